@@ -1,22 +1,27 @@
 """Benchmark of the batched arithmetic-coding stego path (BASELINE.json metric).
 
 Headline (config C3, one MI355X per rank): GPT-2-small (random-init weights of that architecture, fp16 compute,
-fp16 logits) + the HIP coder, B = 4096 independent streams per GPU, each encoding a 1 KiB random payload from
-the shared 32-token context to completion (temp 0.9, precision 26, topk 300, banned {V-1, 628}).  A *step* is
-one lockstep token step over all B streams: the coder step on the current logits, then the batch-invariant GPT-2
-decode step that turns its tokens into the next logits (captured once as a hipGraph and replayed).  The whole
-job is timed: ``value`` = payload bits encoded per second over all ranks, ``ms_per_step`` = job time / lockstep
-steps.  The covers are then decoded (timed separately) and ``roundtrip_exact_fraction`` = share of streams whose
-payload came back bit for bit.
+fp16 logits) + the HIP coder, B = 4096 independent streams per GPU, each encoding a random payload (1 KiB, or as
+many bytes as its steps can consume) from the shared 32-token context (temp 0.9, precision 26, topk 300, banned
+{V-1, 628}).  A *step* is one lockstep token step over all B streams: the coder step on the current logits, then
+the batch-invariant GPT-2 decode step that turns its tokens into the next logits (captured once as a hipGraph and
+replayed).  A plain run times exactly ``--steps`` such steps after ``--warmup`` untimed ones and nothing else:
+``value`` = payload bits encoded per second over all ranks in the timed steps, ``ms_per_step`` = their time /
+``--steps``.  ``--dump-outputs DIR`` writes what the last timed step left a caller (tokens, bits consumed, a
+fixed sample of the next logits) as ``DIR/<name>.npy``; the inputs are the same on every run.
 
-``coder``: the coder hot path alone (SURVEY §8(d)'s roofline unit): ``--steps K`` launches of ``ns_encode_step``
-over B resident [B, ld] synthetic 3*N(0,1) logit batches after ``--warmup W``, the K launches captured as one
-hipGraph and replayed; ``roofline`` is that kernel's (HBM-bound).  ``cpu_baseline``: the oracle port on the host
-cores (rank 0, N = 1).
+``--full`` adds every other measurement to the same JSON line.  ``end_to_end``: the whole C3 job, every stream's
+1 KiB payload encoded to completion through the slot scheduler and timed, then the covers decoded (timed
+separately) with ``roundtrip_exact_fraction`` = share of streams whose payload came back bit for bit.  ``coder``:
+the coder hot path alone (SURVEY §8(d)'s roofline unit): ``--steps K`` launches of ``ns_encode_step`` over B
+resident [B, ld] synthetic 3*N(0,1) logit batches after ``--warmup W``, the K launches captured as one hipGraph
+and replayed; ``roofline`` is that kernel's (HBM-bound).  ``cpu_baseline``: the oracle port on the host cores
+(rank 0, N = 1).  The other configurations (C2, C4, C5, the wide path, ...) are side keys; the ``--no-*``
+switches drop single legs of a ``--full`` run.
 
 Multi-GPU: one process per GPU, each with its own B streams (weak scaling, no collective on the data path; the
-only collectives are the end-of-job reductions).  Launch: python bench.py [--gpus N --steps K --warmup W]; N>1
-under torch.distributed.run.
+only collectives are the end-of-job reductions).  Launch: python bench.py [--gpus N --steps K --warmup W] [--full];
+N>1 under torch.distributed.run.
 """
 
 from __future__ import annotations
@@ -46,8 +51,16 @@ def log(msg: str) -> None:
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200, help="coder sub-benchmark: timed launches")
-    ap.add_argument("--warmup", type=int, default=20, help="coder sub-benchmark: untimed launches")
+    ap.add_argument("--steps", type=int, default=200,
+                    help="timed lockstep steps of the headline (--full: also the coder sub-benchmark's timed launches)")
+    ap.add_argument("--warmup", type=int, default=20,
+                    help="untimed lockstep steps before them (--full: also the coder sub-benchmark's untimed launches)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the whole C3 job with its decode check, the coder "
+                         "sub-benchmarks and rooflines, the other configurations and the CPU baselines (the --no-* "
+                         "switches below drop single legs of such a run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left a caller as DIR/<name>.npy (at most 64 MB)")
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--vocab", type=int, default=50257)
     ap.add_argument("--dtype", default="f32", choices=["f32", "f16"])
@@ -62,7 +75,7 @@ def parse(argv=None):
                     help="end-to-end CPU baseline (HF GPT-2 forward + oracle coder per core); 0 = skip")
     ap.add_argument("--no-e2e", action="store_true",
                     help="skip every end-to-end GPT-2 leg (the headline is then the coder sub-benchmark)")
-    ap.add_argument("--no-decode", action="store_true", help="headline: skip the decode / round-trip check")
+    ap.add_argument("--no-decode", action="store_true", help="whole C3 job: skip the decode / round-trip check")
     ap.add_argument("--no-wide", action="store_true", help="skip the api-default (wide path) side line")
     ap.add_argument("--no-c4", action="store_true",
                     help="skip the gpt2-fa geometry leg (config C4's per-GPU share: 4096 streams, V = 42,001)")
@@ -770,6 +783,154 @@ def coder_bench(args, rank, world, dev, dtype=None, topk=None, pcie=True):
     return out
 
 
+EPOCH_STEPS = 1024  # lockstep steps per pass of the headline: the KV cache of B = 4096 streams then stays on the device
+DUMP_LIMIT = 64 << 20
+
+
+def _sample_rows(n_rows: int, row_bytes: int, budget: int) -> np.ndarray:
+    """Row indices to dump: all of them if they fit ``budget`` bytes, else a fixed (seeded) sorted sample."""
+    keep = max(1, min(n_rows, budget // max(row_bytes, 1)))
+    if keep >= n_rows:
+        return np.arange(n_rows, dtype=np.int64)
+    return np.sort(np.random.default_rng(20251010).choice(n_rows, size=keep, replace=False)).astype(np.int64)
+
+
+def dump_outputs(dirname, arrays) -> None:
+    """``arrays`` (name -> float32 / float64 array) as ``dirname/<name>.npy``, at most ``DUMP_LIMIT`` bytes in all."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT}-byte limit")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError(f"--dump-outputs: {name} is {a.dtype}")
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    log(f"wrote {len(arrays)} arrays ({total} bytes) to {dirname}")
+
+
+def lockstep_steps(args, rank, world, dev, batch=None):
+    """The headline: exactly ``--steps`` timed lockstep steps of the C3 workload after ``--warmup`` untimed ones.
+
+    B streams per GPU start from the shared 32-token context; a step is the slot scheduler's captured step
+    (``lm/slots.py``: ``ns_encode_step`` on the current logits, then the native GPT-2 decode step on its tokens, one
+    hipGraph replay), with every stream's KV pages mapped ahead and no host check in between.  Stream s carries
+    ``synthetic.payload_bytes(s, n)`` with n = ``--e2e-payload-bytes`` or, if the steps can consume more (at most
+    precision - 1 bits each), enough that no stream finishes: the first bytes are the same for every n, so the
+    steps compute the same tokens whatever ``--steps`` is.  The steps run in passes of at most ``EPOCH_STEPS``: a
+    pass starts its streams (the next B * world payloads) at the context again with one untimed step, which also
+    captures the graph; the passes' set-up is not timed.  Returns the result object and the arrays of
+    ``--dump-outputs`` (the last pass's tokens per stream, payload bits consumed, and a sample of the next logits).
+    """
+    import torch
+    import torch.distributed as dist
+
+    from neuralsteganography_amd import synthetic
+    from neuralsteganography_amd.coder import EncodeSession
+    from neuralsteganography_amd.dist import per_rank, reduce_job, shard_range
+    from neuralsteganography_amd.exceptions import KVCapacityError
+    from neuralsteganography_amd.lm.arithmetic import HipArithmeticLM, coder_params_from_quality
+    from neuralsteganography_amd.lm.gpt2 import random_gpt2
+    from neuralsteganography_amd.lm.kvpages import PAGE_ROWS
+    from neuralsteganography_amd.lm.slots import _SlotGraph
+
+    B = batch or args.e2e_batch
+    model = args.e2e_model
+    N, W = int(args.steps), max(0, int(args.warmup))
+    if N < 1:
+        raise SystemExit("--steps must be at least 1")
+    if args.blas:
+        torch.backends.cuda.preferred_blas_library({"rocblas": "cublas", "hipblaslt": "cublaslt"}[args.blas])
+    prov = HipArithmeticLM(random_gpt2(model), None, device=str(dev), logits_dtype=args.e2e_logits, max_batch=B)
+    lm = prov.lm
+    quality = {"temp": args.temp, "precision": args.precision, "topk": args.topk}
+    params = coder_params_from_quality(quality, prov.vocab, prov.logits_dtype, prov.banned)
+    ctx = prov._coder(params, B)
+    context = [prov.vocab - 1] + list(synthetic.DEFAULT_CONTEXT[1:])
+    # passes: (untimed replays, timed replays) after each pass's one untimed first step
+    passes, left = [], N
+    first_warm = max(W - 1, 0)
+    while left > 0:
+        warm = first_warm if not passes else 0
+        room = max(1, EPOCH_STEPS - 1 - warm)
+        passes.append((warm, min(left, room)))
+        left -= passes[-1][1]
+    longest = max(1 + w + n for w, n in passes)
+    lm.warm_pool(pages=B * ((longest + 1 + PAGE_ROWS - 1) // PAGE_ROWS), B=B)  # the timed steps map warm pages
+    timed_s, bits_timed, tok_timed = 0.0, 0, 0
+    sess = logits = None
+    for k, (warm, timed) in enumerate(passes):
+        steps = 1 + warm + timed
+        nbytes = max(int(args.e2e_payload_bytes), ((steps + 1) * args.precision + 7) // 8)
+        ids = [k * B * world + s for s in shard_range(B * world, world, rank)]
+        bits = [np.unpackbits(np.frombuffer(synthetic.payload_bytes(s, nbytes), dtype=np.uint8), bitorder="little")
+                for s in ids]
+        sess = graph = None
+        logits = lm.prefill(context, B, steps + 1)
+        sess = EncodeSession(ctx, bits, max_tokens=steps + 1, payload_stride=nbytes)
+        if not lm.reserve(steps + 1):
+            raise KVCapacityError(f"no device memory for {steps + 1} KV positions of {B} streams")
+
+        def body(sess=sess, logits=logits):
+            lm.step_static(sess.step(logits))
+
+        lm.done_flags = sess.state.view(torch.int32)[:, 7]
+        lm.begin_static(logits)
+        try:
+            graph = _SlotGraph(body)  # one real step on a side stream, then the capture
+            lm.advance(1)
+            for _ in range(warm):
+                graph.replay()
+                lm.advance(1)
+            if world > 1:
+                dist.barrier()
+            torch.cuda.synchronize(dev)
+            f0 = sess.fields()
+            t0 = time.perf_counter()
+            for _ in range(timed):
+                graph.replay()
+                lm.advance(1)
+            torch.cuda.synchronize(dev)
+            timed_s += time.perf_counter() - t0
+        finally:
+            lm.done_flags = None
+            del graph
+        sess.raise_errors()
+        f1 = sess.fields()
+        if int(f1["ntokens"].min()) != steps or bool((f1["flags"] & 1).any()):
+            raise RuntimeError("headline: a stream stopped before its last step")
+        bits_timed += int(f1["bit_pos"].sum() - f0["bit_pos"].sum())
+        tok_timed += int(f1["ntokens"].astype(np.int64).sum() - f0["ntokens"].astype(np.int64).sum())
+    bits_all, tok_all, el_max, _ = reduce_job(bits_timed, tok_timed, timed_s, 0.0, device=dev)
+    out = {"value": bits_all / el_max, "unit": "payload bits/s", "steps": N, "warmup": W,
+           "ms_per_step": 1e3 * el_max / N, "seconds": el_max, "per_rank_seconds": per_rank(timed_s, device=dev),
+           "cover_tokens_per_s": tok_all / el_max, "cover_tokens_per_s_per_gpu": tok_all / el_max / world,
+           "bits_per_token": bits_all / max(tok_all, 1), "payload_bits": bits_all, "cover_tokens": tok_all,
+           "passes": len(passes),
+           "workload": f"{model} (random-init weights, fp16 compute, {args.e2e_logits} logits, fp16 KV cache, "
+                       f"batch-invariant native decode step) + ns_encode_step (temp {args.temp}, precision "
+                       f"{args.precision}, topk {args.topk}), {B} streams/GPU from a 32-token context, {N} timed "
+                       f"lockstep steps (captured hipGraph replays) after {W} untimed, in {len(passes)} pass(es) of at "
+                       f"most {EPOCH_STEPS} steps"}
+    arrays = None
+    if args.dump_outputs and rank == 0:
+        ntok = int(f1["ntokens"].max())
+        rows = _sample_rows(B, ntok * 4, DUMP_LIMIT // 2)
+        lrows = _sample_rows(B, logits.shape[1] * 4, DUMP_LIMIT // 4)
+        ri = torch.from_numpy(rows).to(dev)
+        li = torch.from_numpy(lrows).to(dev)
+        arrays = {"tokens": sess.hist.index_select(0, ri)[:, :ntok].cpu().numpy().astype(np.float32),
+                  "token_rows": rows.astype(np.float64),
+                  "payload_bits_consumed": f1["bit_pos"].astype(np.float64),
+                  "next_logits": logits.index_select(0, li)[:, : prov.vocab].float().cpu().numpy(),
+                  "next_logits_rows": lrows.astype(np.float64)}
+    sess = logits = None
+    lm.release_cache()
+    del prov, lm
+    gc.collect()
+    torch.cuda.empty_cache()
+    return out, arrays
+
+
 def _side_leg(fn):
     """A side line's result, or {"error": ...} if it fails: on one GPU a side line never takes the headline down with
     it (device memory is released before the next leg).  With several ranks a failure propagates: a rank that
@@ -800,6 +961,39 @@ def main():
     dev = torch.device("cuda", local if world > 1 else 0)
     torch.cuda.set_device(dev)
 
+    cfg = {"global_batch": args.batch * world, "vocab": args.vocab, "precision": args.precision, "topk": args.topk,
+           "temp": args.temp, "parallelism": f"dp{world} (independent streams, no collective)"}
+    out = None
+    if not (args.full and args.no_e2e):
+        log(f"C3 lockstep steps ({args.warmup} untimed, {args.steps} timed)")
+        run, arrays = lockstep_steps(args, rank, world, dev)
+        if arrays is not None:
+            dump_outputs(args.dump_outputs, arrays)
+        out = {"metric": METRIC, "value": run["value"], "unit": "payload bits/s", "n_gpus": world,
+               "steps": run["steps"], "warmup": run["warmup"], "ms_per_step": run["ms_per_step"],
+               "per_rank_seconds": run["per_rank_seconds"], "higher_is_better": True, "scaling": "weak",
+               "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+               "config": dict(cfg, workload="C3 lockstep steps: " + run["workload"],
+                              global_batch=args.e2e_batch * world, model=f"{args.e2e_model} (random-init)",
+                              lm_dtype="fp16", logits_dtype=args.e2e_logits, payload_bytes=args.e2e_payload_bytes),
+               "steps_note": "steps = timed lockstep token steps (--steps), after --warmup untimed ones",
+               "cover_tokens_per_s": run["cover_tokens_per_s"],
+               "cover_tokens_per_s_per_gpu": run["cover_tokens_per_s_per_gpu"],
+               "bits_per_token": run["bits_per_token"], "seconds": run["seconds"], "passes": run["passes"]}
+    elif args.dump_outputs:
+        raise SystemExit("--dump-outputs writes the headline's outputs: drop --no-e2e")
+    if args.full:
+        out = full_run(args, rank, world, dev, cfg, out)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def full_run(args, rank, world, dev, cfg, out):
+    """Everything beside the headline (``--full``): the whole C3 job with its decode check, the coder sub-benchmarks
+    and rooflines, the other configurations and the CPU baselines, added to the headline's line ``out`` (None with
+    ``--no-e2e``: the coder sub-benchmark is then the headline)."""
     log("coder sub-benchmark")
     coder = coder_bench(args, rank, world, dev)
     roofline_f32 = coder.pop("roofline")
@@ -817,7 +1011,7 @@ def main():
         side["fraction_coder"] = _side_leg(lambda: fraction_coder(args, rank, world, dev))
     head = None
     if not args.no_e2e:
-        # headline: config C3 end to end, encoded then decoded and checked
+        # the whole C3 job end to end, encoded then decoded and checked
         log("C3 end to end (encode + decode)")
         head = end_to_end(args, rank, world, dev, decode=not args.no_decode)
         if not args.no_c2:  # C2: one message per GPU -- per-token latency of the whole step (small-batch coder form)
@@ -861,23 +1055,10 @@ def main():
         roofline, roofline_side = roofline_f32, roofline_f16
     else:
         roofline, roofline_side = roofline_f16, roofline_f32
-    cfg = {"global_batch": args.batch * world, "vocab": args.vocab, "precision": args.precision, "topk": args.topk,
-           "temp": args.temp, "parallelism": f"dp{world} (independent streams, no collective)"}
-    if head is not None:
-        out = {"metric": METRIC, "value": head["value"], "unit": "payload bits/s", "n_gpus": world,
-               "steps": head["lockstep_steps"], "warmup": args.warmup, "ms_per_step": head["ms_per_step"],
-               "per_rank_seconds": head["per_rank_seconds"], "higher_is_better": True, "scaling": "weak",
-               "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-               "config": dict(cfg, workload="C3 end to end: " + head["workload"], global_batch=args.e2e_batch * world,
-                              model=f"{args.e2e_model} (random-init)", lm_dtype="fp16",
-                              logits_dtype=args.e2e_logits, payload_bytes=args.e2e_payload_bytes),
-               "steps_note": ("steps = lockstep token steps of the timed job (every stream's payload encoded to "
-                              "completion); --steps/--warmup set the coder sub-benchmark"),
-               "cover_tokens_per_s": head["cover_tokens_per_s"],
-               "cover_tokens_per_s_per_gpu": head["cover_tokens_per_s_per_gpu"],
-               "bits_per_token": head["bits_per_token"],
-               "roundtrip_exact_fraction": head.get("roundtrip_exact_fraction"),
-               "roofline": roofline, "end_to_end": head, "coder": coder}
+    if out is not None:
+        # the whole C3 job (every stream's payload encoded to completion, decoded and compared) beside the headline
+        out.update({"roundtrip_exact_fraction": head.get("roundtrip_exact_fraction"), "roofline": roofline,
+                    "end_to_end": head, "coder": coder})
     else:
         out = {"metric": METRIC, "value": coder["value"], "unit": "payload bits/s", "n_gpus": world,
                "steps": args.steps, "warmup": args.warmup, "ms_per_step": coder["ms_per_step"],
@@ -894,10 +1075,7 @@ def main():
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         log("CPU baselines")
         out["cpu_baseline"] = cpu_baseline(args, args.cpu_baseline_seconds)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
+    return out
 
 
 if __name__ == "__main__":

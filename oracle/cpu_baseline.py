@@ -50,7 +50,8 @@ def run(seconds: float, streams: int, seed: int, vocab: int, temp: float, precis
             raise RuntimeError(f"or_encode_batch failed ({rc})")
         steps += 1
     dt = time.perf_counter() - t0
-    return {"bits": int(sum(st[i].bit_pos for i in range(streams))), "stream_steps": steps * streams,
+    # a stream's last step reads up to precision - 1 zero bits past its payload's end: those are no payload bits
+    return {"bits": int(sum(min(st[i].bit_pos, int(nb[i])) for i in range(streams))), "stream_steps": steps * streams,
             "seconds": dt}
 
 

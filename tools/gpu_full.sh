@@ -7,4 +7,4 @@ rc=$?
 echo "pytest rc=$rc" > $o/status.txt
 [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $o/smoke.log 2>&1 && \
-timeout -k 10 900 python bench.py --steps 20 --warmup 5 > $o/bench.json 2> $o/bench.err
+timeout -k 10 900 python bench.py --full --steps 20 --warmup 5 > $o/bench.json 2> $o/bench.err

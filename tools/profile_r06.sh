@@ -12,7 +12,7 @@ mkdir -p "$out"
 export TMPDIR=/tmp
 ver=$(python -c 'from neuralsteganography_amd import _lib; print(_lib.version())')
 echo "library: $ver" > "$out/version.txt"
-coder="bench.py --no-cpu-baseline --no-e2e --no-wide --no-pcie --no-fraction"
+coder="bench.py --full --no-cpu-baseline --no-e2e --no-wide --no-pcie --no-fraction"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$out/coder_trace" -o run --output-format csv -- \
     python $coder > "$out/coder_trace.log" 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
@@ -32,7 +32,7 @@ done
 python tools/pmc_traffic.py "$(find "$out/pmc_attn_FETCH_SIZE" -name '*counter_collection.csv' -print -quit)" \
     "$(find "$out/pmc_attn_WRITE_SIZE" -name '*counter_collection.csv' -print -quit)" "$out/pmc_traffic_attn.json" \
     --version "$ver" --kernel paged_attn_kernel --L 544 --alg-bytes "$alg" --dtype f16 > /dev/null
-wide="bench.py --no-cpu-baseline --no-e2e --no-pcie --no-fraction --no-f16-coder --steps 3 --warmup 1"
+wide="bench.py --full --no-cpu-baseline --no-e2e --no-pcie --no-fraction --no-f16-coder --steps 3 --warmup 1"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$out/wide_trace" -o run --output-format csv -- \
     python $wide > "$out/wide_trace.log" 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
