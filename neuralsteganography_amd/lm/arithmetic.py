@@ -77,37 +77,6 @@ class ByteTokenizer:
 CTX_CACHE_SIZE = 4  # live coder contexts per provider (distinct quality settings)
 
 
-class _StepGraph:
-    """One lockstep encode step -- the HIP coder step on the current logits, then the GPT-2 decode step that
-    turns its tokens into the next logits -- captured once as a hipGraph (``torch.cuda.CUDAGraph``) and replayed
-    per token.  Everything that changes per step lives on the device (coder state, token buffer, the cache
-    length ``d_L``), so a replay issues no host work besides the launch.  Construction runs one real step (on a
-    side stream, which also warms up every kernel and GEMM plan) before capturing the next."""
-
-    def __init__(self, lm, coder_step, logits):
-        import torch
-
-        self.lm, self.coder_step = lm, coder_step  # coder_step(logits) -> the step's token buffer [B] (device)
-        self.logits = logits.clone()
-        lm.begin_static(self.logits)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            self._body()
-        torch.cuda.current_stream().wait_stream(side)
-        lm.L += 1
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self._body()
-
-    def _body(self) -> None:
-        self.lm.step_static(self.coder_step(self.logits))
-
-    def replay(self) -> None:
-        self.graph.replay()
-        self.lm.L += 1
-
-
 class _StopCheck:
     """The reference's per-token stop test ``stop_text in enc.decode(output)`` (``code_base/arithmetic.py:
     207-210``) without a host round trip per token.  A new occurrence of ``stop_text`` must end inside the newest
@@ -309,11 +278,10 @@ class HipArithmeticLM:
         A message's tokens do not depend on its slot or neighbours (batch-invariant decode step).  Other LMs (the
         PyTorch fp32 forward, synthetic rows) run the lockstep loop below.
 
-        With ``graphs`` (default; needs the native fp16 step) the per-token step is captured once as a hipGraph
-        and replayed, which removes the per-launch host cost (it dominates at small batch, and at B = 4096 it
-        keeps the GPU busy across the host checks); the cache budget bounds the replays and the loop continues
-        eagerly (growing the cache) if it runs out.  The token history starts at the KV budget: when a stream
-        would outgrow it, the graph is dropped, the history grown and the step captured again.
+        With ``graphs`` (default) the native model's per-token step is captured once as a hipGraph and replayed,
+        which removes the per-launch host cost (it dominates at small batch, and at B = 4096 it keeps the GPU busy
+        across the host checks).  Non-native models ignore ``graphs``: their lockstep loop runs eagerly, and its token
+        history starts at the KV budget and grows at the host checks.
 
         The reference coder has no underflow handling: when the interval straddles the midpoint and one
         token takes the whole range, no bit is ever fixed and ``code_base/arithmetic.py:114`` loops
@@ -351,10 +319,8 @@ class HipArithmeticLM:
         if finish:
             ctx.set_sentence_end(self.sentence_end_table())
         logits = self.lm.prefill(context, B, budget)
-        use_graph = graphs and getattr(self.lm, "hip_attention", False) and hasattr(self.lm, "begin_static")
-        # token history: starts at the KV budget and grows at the host checks (a captured graph holds the
-        # buffer's address, so it is re-captured after a growth; the 64x hard cap up front would be 8.6 GB at
-        # B = 4096)
+        # token history: starts at the KV budget and grows at the host checks (the 64x hard cap up front would be
+        # 8.6 GB at B = 4096)
         sess = EncodeSession(ctx, bit_lists, max_tokens=budget, stats=return_stats)
         stop = _StopCheck(self, sess, stop_text) if stop_text is not None else None
 
@@ -364,17 +330,7 @@ class HipArithmeticLM:
                 stop.flag(tok)  # device-side: did any live stream emit a token that can complete stop_text?
             return tok
 
-        native = getattr(self.lm, "native", False) and self.skip_done
-        if native:  # finished streams skip their attention reads (the coder state's flags word, NS_ST_DONE)
-            import torch
-
-            self.lm.done_flags = sess.state.view(torch.int32)[:, 7]
-        try:
-            toks = self._encode_loop(sess, coder_step, logits, stop, bit_lists, check_every, stall_steps, hard_cap,
-                                     use_graph)
-        finally:
-            if native:
-                self.lm.done_flags = None
+        toks = self._encode_loop(sess, coder_step, logits, stop, bit_lists, check_every, stall_steps, hard_cap)
         for b in bit_lists:
             st = _bits_count_state(len(b))
             self._encode_states.append(st)
@@ -383,12 +339,12 @@ class HipArithmeticLM:
             return toks, sess.stats()
         return toks
 
-    def _encode_loop(self, sess, coder_step, logits, stop, bit_lists, check_every, stall_steps, hard_cap, use_graph):
+    def _encode_loop(self, sess, coder_step, logits, stop, bit_lists, check_every, stall_steps, hard_cap):
+        """The eager lockstep loop of the non-native models: every stream steps until all are done."""
         B = sess.B
         t = 0
         last_pos = None
         last_move = 0
-        graph = None
         while True:
             if stop is not None and t > 0:
                 stop.check()  # code_base/arithmetic.py:207-210 ('<eos>' in run_single.py's message->bits mode)
@@ -396,10 +352,7 @@ class HipArithmeticLM:
                 f = sess.fields()
                 if bool((f["flags"] & 1).all()):
                     break
-                if graph is not None and int(f["ntokens"].max(initial=0)) + check_every + 1 > sess.hist.shape[1]:
-                    logits, graph = graph.logits, None  # the history must grow: re-capture with the new buffer
-                if graph is None:
-                    sess.ensure_history(check_every + 1)
+                sess.ensure_history(check_every + 1)
                 pos = f["bit_pos"].copy()
                 if last_pos is None or (pos != last_pos).any():
                     last_pos, last_move = pos, t
@@ -415,19 +368,9 @@ class HipArithmeticLM:
                         f"streams {stuck[:8]} fixed no payload bit for {t - last_move} tokens: the interval "
                         "straddles the midpoint and one token takes the whole range (the reference coder "
                         "has no underflow handling and would loop forever)")
-            if use_graph and self.lm.static_capacity_left() >= 1:
-                if graph is None:
-                    graph = _StepGraph(self.lm, coder_step, logits)
-                else:
-                    graph.replay()
-                t += 1
-                continue
-            if graph is not None:  # the preallocated cache is used up: continue eagerly (the cache grows)
-                logits, graph, use_graph = graph.logits, None, False
             tok = coder_step(logits)
             logits = self.lm.step(tok)
             t += 1
-        del graph
         return sess.tokens()
 
     def decode_batch(self, token_lists: Sequence[Sequence[int]], context: Sequence[int], *,
@@ -436,9 +379,7 @@ class HipArithmeticLM:
         """Decode token lists (ragged); returns every emitted bit (callers truncate).  On the native GPU model the
         lists run through ``slots`` slots (:class:`~neuralsteganography_amd.lm.slots.SlotDecoder`, longest first,
         a message's pages mapped when it is admitted); with ``graphs`` the per-token step (coder + GPT-2 decode) is a
-        replayed hipGraph, as in :meth:`encode_batch`."""
-        import torch
-
+        replayed hipGraph, as in :meth:`encode_batch`.  Non-native models ignore ``graphs`` (eager lockstep loop)."""
         from ..codec.errors import DecodeDivergenceError
 
         B = len(token_lists)
@@ -462,30 +403,11 @@ class HipArithmeticLM:
         ctx = self._coder(params, B)
         sess = DecodeSession(ctx, token_lists)
         logits = self.lm.prefill(context, B, max(sess.T, 1) + 1)
-        native = getattr(self.lm, "native", False) and self.skip_done
-        if native:
-            # the forward after token t feeds token t + 1's logits: a stream of n tokens needs none once the cache
-            # length reaches prefill + n - 1, so its attention is skipped from there (ragged, uneven covers)
-            import torch
-
-            lens = torch.tensor([len(t) for t in token_lists], dtype=torch.int32)
-            self.lm.stop_len = (lens + (self.lm.L - 1)).to(self.lm.device)
-        try:
-            if (graphs and sess.T > 2 and getattr(self.lm, "hip_attention", False) and hasattr(self.lm, "begin_static")
-                    and self.lm.static_capacity_left() >= sess.T):  # replays cannot grow the cache
-                graph = _StepGraph(self.lm, sess.step_static, logits)  # runs token 0, captures the next step
-                for _ in range(1, sess.T):  # the last replay's forward feeds nothing (the cache holds T + 1)
-                    graph.replay()
-                del graph
-                return sess.bits()
-            for t in range(sess.T):
-                sess.step(logits)
-                if t + 1 < sess.T:
-                    logits = self.lm.step(sess.tok[t])
-            return sess.bits()
-        finally:
-            if native:
-                self.lm.stop_len = None
+        for t in range(sess.T):
+            sess.step(logits)
+            if t + 1 < sess.T:
+                logits = self.lm.step(sess.tok[t])
+        return sess.bits()
 
     def decode_counted(self, token_lists: Sequence[Sequence[int]], context: Sequence[int], *,
                        quality: Mapping[str, object], done=None, check_every: int = 64):

@@ -1,8 +1,8 @@
-"""Batched GPT-2 forward with a preallocated KV cache, writing logits straight into the coder's layout.
+"""Batched GPT-2 forward with a KV cache, writing logits straight into the coder's layout.
 
-This is the L1 "LM runtime" of SURVEY.md §1 rebuilt for batch B (PyTorch-ROCm holds the weights and the KV cache;
-in the fp16 GPU configuration every GEMM and attention of the forward runs on the library's own MFMA kernels, see
-below).  It reproduces the reference's forward semantics (``code_base/arithmetic.py:12-48,115-122``):
+This is the L1 "LM runtime" of SURVEY.md §1 rebuilt for batch B (PyTorch-ROCm holds the weights; in the fp16 GPU
+configuration every GEMM and attention of the forward runs on the library's own MFMA kernels over a paged KV cache,
+see below).  It reproduces the reference's forward semantics (``code_base/arithmetic.py:12-48,115-122``):
 
 * the first call runs the whole context with default positions ``0..T-1``;
 * every later call feeds ONE token per stream with ``position_ids = cache_len % n_positions``
@@ -12,11 +12,12 @@ below).  It reproduces the reference's forward semantics (``code_base/arithmetic
 In fp16 on the GPU (the product configuration) every forward runs on hand-written HIP kernels whose per-stream
 results do not depend on the batch size (``include/nsg_lm.h``: MFMA GEMMs with the bias / gelu / residual
 epilogues fused, layer norms, embedding; ``include/nsg_attn.h``: the decode step's KV append fused with a
-fixed-split online-softmax attention, HBM-bound on the cache, and a causal MFMA flash attention for whole
-sequences): the decode steps, the shared-context prefill, the guard's scoring forward and the ``max_context``
-window forward.  A cover encoded in a batch of B streams decodes to the same logits alone, and a text scores the
-same alone or in a batch.  fp32 compute and the CPU keep PyTorch (``addmm`` + ``scaled_dot_product_attention``) as
-the forward's reference configuration (tests pin the two against each other and against Hugging Face).
+fixed-split online-softmax attention over each stream's pages (``lm/kvpages.py``), HBM-bound on the cache, and a
+causal MFMA flash attention for whole sequences): the decode steps, the shared-context prefill, the guard's scoring
+forward and the ``max_context`` window forward.  A cover encoded in a batch of B streams decodes to the same logits
+alone, and a text scores the same alone or in a batch.  fp32 compute and the CPU keep PyTorch (``addmm`` +
+``scaled_dot_product_attention`` over a dense ``k_cache``/``v_cache``) as the forward's reference configuration
+(tests pin the two against each other and against Hugging Face).
 
 Logits are produced as ``h @ wte^T`` into a ``[B, ld]`` buffer with ``ld = row_stride(V)`` (zero weight
 columns beyond V), so the coder reads 16-byte-aligned rows without a copy.  Weights are taken from a
@@ -48,7 +49,8 @@ class GPT2Shape:
 
 
 class BatchedGPT2:
-    """GPT-2 decoder for B streams in lockstep.
+    """GPT-2 decoder for B streams: one token per stream and step, each stream at its own cache length on the
+    native path (``kv``, the page table the slot schedulers drive), all at ``L`` on the PyTorch path.
 
     ``compute_dtype`` is the weight/activation dtype (fp16 on the GPU by default); ``logits_dtype`` is what
     the coder reads (``torch.float32`` or ``torch.float16``)."""
@@ -96,19 +98,17 @@ class BatchedGPT2:
         self.L = 0
         self.T0 = 0  # positions held once in the shared prefix cache (kp, vp) instead of per stream
         self.position_cap = None  # optional cap on the initial per-stream cache length (the cache still grows)
-        self.chunked_cache = True  # native decode: chunk-plane KV layout (False: plain per-pair rows; A/B only)
         # attention window (opt-in, 0 = the reference's unbounded cache): decode steps attend to the last `window`
         # positions only -- a sliding-window approximation bounding the per-step KV traffic (native path only)
         self.window = 0
         self.kp = self.vp = None
-        self.k_cache = self.v_cache = None
+        self.k_cache = self.v_cache = None  # dense [layer, B, H, rows, D] cache of the PyTorch path only
         # Decode steps in fp16 on the GPU run entirely on the batch-invariant HIP kernels (include/nsg_lm.h and
         # the fixed-split attention of include/nsg_attn.h; fail loudly if the library is missing): a stream's
         # logits are bit-identical whatever the batch it runs in, so a cover encoded among B streams decodes
         # alone.  Weights are kept transposed ([N, K], K contiguous).  fp32 compute and the CPU keep the PyTorch
         # path (SDPA), the forward's reference configuration in the tests.
         self.native = self.device.type == "cuda" and self.dtype == torch.float16
-        self.hip_attention = self.native  # graph capture needs the native step (kept name: callers probe it)
         # KV cache element type: "fp16" (the reference configuration) or "fp8" (OCP e4m3fn, opt-in: half the
         # bytes the HBM-bound decode attention reads; logits differ at the fp8 quantisation level, the same for
         # encoder and decoder, batch-invariant)
@@ -131,19 +131,10 @@ class BatchedGPT2:
         # optional per-stream stop positions (int32 [B]): a stream whose cache length reached its stop skips its
         # attention (decode: the position after which its logits are no longer read)
         self.stop_len = None
-        # decode-step lanes (native path): 2 = the batch's two row halves on two streams with alternating attention
-        # launches (one half's GEMMs overlap the other's attention); 1 = one launch chain
-        self.decode_lanes = 1
-        self.decode_lanes_min_batch = 1024
-        self.decode_lanes_order = "alternate"  # or "free": no ordering between the lanes; "split": attention stream +
-        # GEMM stream
-        self.decode_lane_cu_split = None  # "split": fraction of each XCD's CUs masked to the attention stream
-        self._side = None
-        self._split = None
         if self.native:
             from .. import _lib
 
-            self._attn = _lib.lib().ns_decode_attention_ex
+            _lib.lib()  # a missing library fails here, not at the first step
             self._kv_format = _lib.NS_KV_FP8 if kv_dtype == "fp8" else _lib.NS_KV_FP16
             if self.shape.n_embd // self.shape.n_head != 64:
                 raise ValueError("the HIP decode attention needs head_dim 64 (GPT-2 small/medium/large)")
@@ -199,21 +190,9 @@ class BatchedGPT2:
                         "f": torch.empty((B, 4 * C), device=dev, dtype=dt)}
         return self._nb
 
-    def _cache_shape(self, B: int, rows: int, plain: bool):
+    def _cache_shape(self, B: int, rows: int):
         s = self.shape
-        hd = s.n_embd // s.n_head
-        if plain:
-            return (s.n_layer, B, s.n_head, rows, hd)
-        # chunk planes: [layer][rows/32][B][H][32][D] -- the rows a decode step reads stay dense in memory
-        # whatever the capacity (fewer pages touched than per-pair row ranges padded to the capacity)
-        return (s.n_layer, (rows + 31) // 32, B, s.n_head, 32, hd)
-
-    def _cache_strides(self, layer: int):
-        """(b, h, chunk) element strides of one layer's stream cache for the attention kernels."""
-        kc = self.k_cache[layer]
-        if kc.dim() == 5:  # chunk planes [nch, B, H, 32, D]
-            return kc.stride(1), kc.stride(2), kc.stride(0)
-        return kc.stride(0), kc.stride(1), 0  # plain [B, H, rows, D]
+        return (s.n_layer, B, s.n_head, rows, s.n_embd // s.n_head)
 
     def _allocate_fitted(self, B: int, base: int, want: int, T0: int = 0) -> None:
         """allocate(B, base + fit_positions(B, want)), falling back to a fresh budget after releasing PyTorch's
@@ -225,18 +204,14 @@ class BatchedGPT2:
             torch.cuda.empty_cache()
             self.allocate(B, base + self.fit_positions(B, want, count_cached=False), T0=T0)
 
-    def allocate(self, B: int, max_len: int, T0: int = 0, dtype=None, plain=None) -> None:
-        """Per-stream KV cache for absolute positions [T0, max_len): positions below T0 (the shared context,
-        native path only) live once in ``kp``/``vp`` instead of B times.  The native decode step keeps the cache
-        in chunk planes (``plain`` False); the PyTorch path (and the prefill) in plain [B, H, rows, D] rows."""
+    def allocate(self, B: int, max_len: int, T0: int = 0) -> None:
+        """Dense per-stream KV cache of the PyTorch path (``k_cache``/``v_cache``, plain [layer, B, H, rows, D]
+        rows) for absolute positions [T0, max_len).  The native path pages instead (:meth:`begin_slots`)."""
         self.k_cache = self.v_cache = None
-        if plain is None:
-            plain = not self.native or not self.chunked_cache
-        shp = self._cache_shape(B, max_len - T0, plain)
+        shp = self._cache_shape(B, max_len - T0)
         # uninitialised: attention only ever reads positions < L + 1, all written before they are read
-        kdt = self.kv_torch_dtype if dtype is None else dtype
-        self.k_cache = torch.empty(shp, device=self.device, dtype=kdt)
-        self.v_cache = torch.empty(shp, device=self.device, dtype=kdt)
+        self.k_cache = torch.empty(shp, device=self.device, dtype=self.kv_torch_dtype)
+        self.v_cache = torch.empty(shp, device=self.device, dtype=self.kv_torch_dtype)
         self.B, self.L, self.max_len, self.T0 = B, 0, max_len, T0
         if T0 == 0:
             self.kp = self.vp = None
@@ -256,17 +231,11 @@ class BatchedGPT2:
             if new_len <= self.L:
                 raise KVCapacityError(f"KV cache full at {self.L} positions for B={self.B}: no device memory to grow")
         T0, n = self.T0, self.L - self.T0  # stream rows filled so far
-        plain = self.k_cache.dim() == 5
-        shp = self._cache_shape(self.B, new_len - T0, plain)
+        shp = self._cache_shape(self.B, new_len - T0)
         k = torch.empty(shp, device=self.device, dtype=self.k_cache.dtype)
         v = torch.empty(shp, device=self.device, dtype=self.v_cache.dtype)
-        if plain:
-            k[:, :, :, :n] = self.k_cache[:, :, :, :n]
-            v[:, :, :, :n] = self.v_cache[:, :, :, :n]
-        else:
-            nch = (n + 31) // 32  # whole chunk planes: the rows beyond n are never read before written
-            k[:, :nch] = self.k_cache[:, :nch]
-            v[:, :nch] = self.v_cache[:, :nch]
+        k[:, :, :, :n] = self.k_cache[:, :, :, :n]
+        v[:, :, :, :n] = self.v_cache[:, :, :, :n]
         self.k_cache, self.v_cache, self.max_len = k, v, new_len
 
     def _ln(self, x, wgt, b):
@@ -311,9 +280,8 @@ class BatchedGPT2:
         out = torch.empty(src.shape, device=src.device, dtype=torch.uint8)
         if src.numel() % 4:
             raise ValueError("fp8 quantisation needs a multiple of 4 elements")
-        rc = _lib.lib().ns_quantize_fp8(src.data_ptr(), out.data_ptr(), src.numel(), _stream_handle())
-        if rc != 0:
-            raise RuntimeError(f"ns_quantize_fp8 failed ({rc})")
+        _check(_lib.lib().ns_quantize_fp8(src.data_ptr(), out.data_ptr(), src.numel(), _stream_handle()),
+               "ns_quantize_fp8")
         return out
 
     @torch.no_grad()
@@ -394,31 +362,26 @@ class BatchedGPT2:
         f = torch.empty((M, 4 * C), device=dev, dtype=dt)
         eps = float(s.eps)
 
-        def ok(rc, what):
-            if rc != 0:
-                raise RuntimeError(f"{what} failed ({rc})")
-
         def gemm(x, wt, bias, y, epi, N, K):
-            ok(L.ns_lm_gemm(x.data_ptr(), x.stride(0), wt.data_ptr(), wt.stride(0),
-                            bias.data_ptr() if bias is not None else None, y.data_ptr(), y.stride(0), M, N, K, epi,
-                            st), "ns_lm_gemm")
+            _check(L.ns_lm_gemm(x.data_ptr(), x.stride(0), wt.data_ptr(), wt.stride(0), bias.data_ptr(),
+                                y.data_ptr(), y.stride(0), M, N, K, epi, st), "ns_lm_gemm")
 
         def ln(x, w, b, y):
-            ok(L.ns_lm_layernorm(x.data_ptr(), C, w.data_ptr(), b.data_ptr(), y.data_ptr(), C, M, C, eps, st),
-               "ns_lm_layernorm")
+            _check(L.ns_lm_layernorm(x.data_ptr(), C, w.data_ptr(), b.data_ptr(), y.data_ptr(), C, M, C, eps, st),
+                   "ns_lm_layernorm")
 
         lw0 = self.layers[0]
-        ok(L.ns_lm_embed_seq_ln(tok.data_ptr(), self.wte.data_ptr(), self.wpe.data_ptr(), s.vocab, s.n_positions, T,
-                                h.data_ptr(), C, lw0["ln1_w"].data_ptr(), lw0["ln1_b"].data_ptr(), a.data_ptr(), C, M,
-                                C, eps, st), "ns_lm_embed_seq_ln")
+        _check(L.ns_lm_embed_seq_ln(tok.data_ptr(), self.wte.data_ptr(), self.wpe.data_ptr(), s.vocab, s.n_positions,
+                                    T, h.data_ptr(), C, lw0["ln1_w"].data_ptr(), lw0["ln1_b"].data_ptr(),
+                                    a.data_ptr(), C, M, C, eps, st), "ns_lm_embed_seq_ln")
         for i, lw in enumerate(self.layers):
             if i > 0:
                 ln(h, lw["ln1_w"], lw["ln1_b"], a)
             gemm(a, lw["qkv_wt"], lw["qkv_b"], qkv, _lib.NS_LM_EPI_STORE, 3 * C, C)
             if kv_hook is not None:
                 kv_hook(i, qkv)
-            ok(L.ns_seq_attention(qkv.data_ptr(), qkv.stride(0), o.data_ptr(), o.stride(0), B, T, H, D,
-                                  1.0 / math.sqrt(D), st), "ns_seq_attention")
+            _check(L.ns_seq_attention(qkv.data_ptr(), qkv.stride(0), o.data_ptr(), o.stride(0), B, T, H, D,
+                                      1.0 / math.sqrt(D), st), "ns_seq_attention")
             gemm(o, lw["o_wt"], lw["o_b"], h, _lib.NS_LM_EPI_RESIDUAL, C, C)
             ln(h, lw["ln2_w"], lw["ln2_b"], a)
             gemm(a, lw["fc_wt"], lw["fc_b"], f, _lib.NS_LM_EPI_GELU, 4 * C, C)
@@ -436,16 +399,12 @@ class BatchedGPT2:
         hrows = hrows.contiguous()
         R = hrows.shape[0]
         a = torch.empty_like(hrows)
-        rc = L.ns_lm_layernorm(hrows.data_ptr(), C, self.lnf_w.data_ptr(), self.lnf_b.data_ptr(), a.data_ptr(), C, R,
-                               C, float(self.shape.eps), st)
-        if rc != 0:
-            raise RuntimeError(f"ns_lm_layernorm failed ({rc})")
+        _check(L.ns_lm_layernorm(hrows.data_ptr(), C, self.lnf_w.data_ptr(), self.lnf_b.data_ptr(), a.data_ptr(), C,
+                                 R, C, float(self.shape.eps), st), "ns_lm_layernorm")
         out = torch.empty((R, self.ld), device=self.device, dtype=self.logits_dtype)
         epi = _lib.NS_LM_EPI_STORE_F32 if out.dtype == torch.float32 else _lib.NS_LM_EPI_STORE
-        rc = L.ns_lm_gemm(a.data_ptr(), C, self.head_t.data_ptr(), self.head_t.stride(0), None, out.data_ptr(),
-                          out.stride(0), R, self.ld, C, epi, st)
-        if rc != 0:
-            raise RuntimeError(f"ns_lm_gemm failed ({rc})")
+        _check(L.ns_lm_gemm(a.data_ptr(), C, self.head_t.data_ptr(), self.head_t.stride(0), None, out.data_ptr(),
+                            out.stride(0), R, self.ld, C, epi, st), "ns_lm_gemm")
         return out
 
     @torch.no_grad()
@@ -585,154 +544,30 @@ class BatchedGPT2:
         stop_ptr = sl.data_ptr() if sl is not None else None
         if out.shape != (B, self.ld) or out.stride(1) != 1:
             raise ValueError(f"logits buffer must be [{B}, {self.ld}]")
-        lanes = self._lanes(B)
-        if len(lanes) == 1:
-            self._decode_rows(L, st, tok, out, 0, B, done_ptr, done_stride, stop_ptr)
-            return out
-        main = torch.cuda.current_stream(self.device)
-        if self.decode_lanes_order == "split":
-            return self._decode_split(L, main, tok, out, lanes, done_ptr, done_stride, stop_ptr)
-        # two lanes (row halves) on two streams, their attention launches alternating (lane 0 layer i, lane 1 layer
-        # i, lane 0 layer i + 1, ...): one lane's GEMMs / layer norms run beside the other lane's HBM-bound attention
-        # instead of after it.  Rows are independent (batch invariance), so the bits are those of one launch chain.
-        side = self._side_stream()
-        fork = torch.cuda.Event()
-        fork.record(main)
-        side.wait_event(fork)
-        (r0, n0), (r1, n1) = lanes
-        steps = [self._decode_rows(L, st, tok, out, r0, n0, done_ptr, done_stride, stop_ptr, gen=True),
-                 self._decode_rows(L, side.cuda_stream, tok, out, r1, n1, done_ptr, done_stride, stop_ptr, gen=True)]
-        streams = (main, side)
-        alternate = self.decode_lanes_order == "alternate"
-        prev = None  # (lane, event after its latest attention launch)
-        for _ in range(self.shape.n_layer):
-            for k in (0, 1):
-                next(steps[k])  # up to the attention launch
-                if alternate and prev is not None:
-                    streams[k].wait_event(prev[1])
-                next(steps[k])  # the attention launch
-                if alternate:
-                    ev = torch.cuda.Event()
-                    ev.record(streams[k])
-                    prev = (k, ev)
-        for k in (0, 1):
-            for _ in steps[k]:  # ln_f and the head
-                pass
-        join = torch.cuda.Event()
-        join.record(side)
-        main.wait_event(join)
-        return out
-
-    def _decode_split(self, L, main, tok, out, lanes, done_ptr, done_stride, stop_ptr):
-        """Two lanes, the attention launches on one stream (lane 0 layer i, lane 1 layer i, lane 0 layer i + 1, ...)
-        and every other launch on a second one: lane k's GEMMs of layer i run while lane 1-k's attention of layer i
-        streams.  With ``decode_lane_cu_split`` the two streams are CU-masked (that fraction of every XCD's CUs for the
-        attention stream, the rest for the other), so the GEMMs get CUs while the attention holds the rest."""
-        if torch.cuda.is_current_stream_capturing():  # measured: the runtime crashes ending such a capture, and a
-            raise RuntimeError("split decode lanes run eagerly only (graphs=False)")  # graph drops the CU masks
-        sa, sg = self._split_streams()
-        fork = torch.cuda.Event()
-        fork.record(main)
-        sg.wait_event(fork)
-        sa.wait_event(fork)
-        gens = [self._decode_rows_gen(L, sg.cuda_stream, tok, out, r, n, done_ptr, done_stride, stop_ptr,
-                                      st_attn=sa.cuda_stream) for r, n in lanes]
-        att = [None, None]  # event after each lane's latest attention launch
-        for _ in range(self.shape.n_layer):
-            for k in (0, 1):
-                if att[k] is not None:
-                    sg.wait_event(att[k])
-                next(gens[k])  # lane k: the launches before its attention (on sg)
-                ev = torch.cuda.Event()
-                ev.record(sg)
-                sa.wait_event(ev)
-                next(gens[k])  # its attention (on sa)
-                att[k] = torch.cuda.Event()
-                att[k].record(sa)
-        for k in (0, 1):
-            sg.wait_event(att[k])
-            for _ in gens[k]:  # the last layer's GEMMs, ln_f and the head
-                pass
-        for stream in (sg, sa):  # both streams rejoin the caller's directly (a graph capture ends on it)
-            join = torch.cuda.Event()
-            join.record(stream)
-            main.wait_event(join)
-        return out
-
-    def _split_streams(self):
-        if self._split is None:
-            frac = self.decode_lane_cu_split
-            if frac is None:
-                self._split = (torch.cuda.Stream(self.device), torch.cuda.Stream(self.device))
-            else:
-                self._split = (_cu_masked_stream(self.device, frac, True), _cu_masked_stream(self.device, frac, False))
-        return self._split
-
-    def _lanes(self, B: int):
-        """Row ranges of the decode step's lanes: one, or two halves (``decode_lanes`` = 2) when B is large enough
-        for both halves to fill the chip."""
-        if self.decode_lanes <= 1 or B < max(2, self.decode_lanes_min_batch):
-            return [(0, B)]
-        h = (B // 2 + 15) // 16 * 16  # 16-row aligned split (whole MFMA row blocks in lane 0)
-        if not 0 < h < B:
-            h = B // 2
-        return [(0, h), (h, B - h)]
-
-    def _side_stream(self):
-        if self._side is None:
-            self._side = torch.cuda.Stream(self.device)
-        return self._side
-
-    def _decode_rows(self, L, st, tok, out, r0, n, done_ptr, done_stride, stop_ptr, gen=False):
-        """The decode step's launches for rows [r0, r0 + n) on stream ``st``.  ``gen``: a generator that yields
-        before and after each layer's attention launch (the caller orders the lanes' attention launches)."""
-        it = self._decode_rows_gen(L, st, tok, out, r0, n, done_ptr, done_stride, stop_ptr)
-        if gen:
-            return it
-        for _ in it:
-            pass
-
-    def _decode_rows_gen(self, L, st, tok, out, r0, B, done_ptr, done_stride, stop_ptr, st_attn=None):
-        from .. import _lib
-
-        st_attn = st if st_attn is None else st_attn
+        if B < 1:
+            raise ValueError("decode step over an empty batch")
         s = self.shape
-        kv = self.kv
         C = s.n_embd
         H, D = s.n_head, C // s.n_head
-        nb = self._native_buffers(kv.B)
-        if not (B > 0 and r0 >= 0 and r0 + B <= kv.B):  # host check before any launch: rows inside every buffer
-            raise ValueError(f"decode rows [{r0}, {r0 + B}) outside the batch of {kv.B}")
-
-        def row(t, r=r0):  # address of row r of a [*, ...] tensor
-            return t.data_ptr() + r * t.stride(0) * t.element_size()
-
-        h, a, qkv, o, f = (row(nb[k]) for k in ("h", "a", "qkv", "o", "f"))
+        nb = self._native_buffers(B)
+        h, a, qkv, o, f = (nb[k].data_ptr() for k in ("h", "a", "qkv", "o", "f"))
         ldq, ldf = nb["qkv"].stride(0), nb["f"].stride(0)
         T0 = kv.T0
         eps = float(s.eps)
 
-        def ok(rc, what):
-            if rc != 0:
-                raise RuntimeError(f"{what} failed ({rc})")
-
         def gemm(x, ldx, wt, bias, y, ldy, epi, N, K):
-            ok(L.ns_lm_gemm(x, ldx, wt.data_ptr(), wt.stride(0), bias.data_ptr() if bias is not None else None, y,
-                            ldy, B, N, K, epi, st), "ns_lm_gemm")
-
-        lens = row(kv.lens)
-        lw0 = self.layers[0]
-        ok(L.ns_lm_embed_ln_rows(row(tok), self.wte.data_ptr(), self.wpe.data_ptr(), s.vocab, s.n_positions,
-                                 lens, h, C, lw0["ln1_w"].data_ptr(), lw0["ln1_b"].data_ptr(), a, C, B, C, eps, st),
-           "ns_lm_embed_ln_rows")
+            _check(L.ns_lm_gemm(x, ldx, wt.data_ptr(), wt.stride(0), bias.data_ptr() if bias is not None else None,
+                                y, ldy, B, N, K, epi, st), "ns_lm_gemm")
 
         def ln_gemm(ln_w, ln_b, wt, bias, y, ldy, epi, N):  # ln(h) -> GEMM, one launch at small B (same bits)
-            ok(L.ns_lm_ln_gemm(h, C, ln_w.data_ptr(), ln_b.data_ptr(), eps, wt.data_ptr(), wt.stride(0),
-                               bias.data_ptr(), y, ldy, B, N, C, epi, a, C, st), "ns_lm_ln_gemm")
+            _check(L.ns_lm_ln_gemm(h, C, ln_w.data_ptr(), ln_b.data_ptr(), eps, wt.data_ptr(), wt.stride(0),
+                                   bias.data_ptr(), y, ldy, B, N, C, epi, a, C, st), "ns_lm_ln_gemm")
 
-        table = row(kv.table)
-        done = done_ptr + r0 * done_stride * 4 if done_ptr else None
-        stop = stop_ptr + r0 * 4 if stop_ptr else None
+        lens, table = kv.lens.data_ptr(), kv.table.data_ptr()
+        lw0 = self.layers[0]
+        _check(L.ns_lm_embed_ln_rows(tok.data_ptr(), self.wte.data_ptr(), self.wpe.data_ptr(), s.vocab,
+                                     s.n_positions, lens, h, C, lw0["ln1_w"].data_ptr(), lw0["ln1_b"].data_ptr(), a,
+                                     C, B, C, eps, st), "ns_lm_embed_ln_rows")
         for i, lw in enumerate(self.layers):
             if i > 0:
                 ln_gemm(lw["ln1_w"], lw["ln1_b"], lw["qkv_wt"], lw["qkv_b"], qkv, ldq, _lib.NS_LM_EPI_STORE, 3 * C)
@@ -740,22 +575,20 @@ class BatchedGPT2:
                 gemm(a, C, lw["qkv_wt"], lw["qkv_b"], qkv, ldq, _lib.NS_LM_EPI_STORE, 3 * C, C)
             kp = self.kp[i, 0] if T0 else None  # [H, T0, D]
             vp = self.vp[i, 0] if T0 else None
-            yield  # before the attention launch
-            rc = L.ns_decode_attention_paged(qkv, ldq, table, kv.table.stride(0), kv.width, kv.pool.layer_offset(i),
-                                             kp.data_ptr() if T0 else None, vp.data_ptr() if T0 else None,
-                                             kp.stride(0) if T0 else 0, T0, B, H, D, lens, self.window,
-                                             self._kv_format, done, done_stride, stop, o, C, 1.0 / math.sqrt(D),
-                                             st_attn)
-            ok(rc, "ns_decode_attention_paged")
-            yield  # after it
+            _check(L.ns_decode_attention_paged(qkv, ldq, table, kv.table.stride(0), kv.width,
+                                               kv.pool.layer_offset(i), kp.data_ptr() if T0 else None,
+                                               vp.data_ptr() if T0 else None, kp.stride(0) if T0 else 0, T0, B, H, D,
+                                               lens, self.window, self._kv_format, done_ptr, done_stride, stop_ptr,
+                                               o, C, 1.0 / math.sqrt(D), st), "ns_decode_attention_paged")
             gemm(o, C, lw["o_wt"], lw["o_b"], h, C, _lib.NS_LM_EPI_RESIDUAL, C, C)
             ln_gemm(lw["ln2_w"], lw["ln2_b"], lw["fc_wt"], lw["fc_b"], f, ldf, _lib.NS_LM_EPI_GELU, 4 * C)
             gemm(f, ldf, lw["pr_wt"], lw["pr_b"], h, C, _lib.NS_LM_EPI_RESIDUAL, C, 4 * C)
         # ln_f also advances every stream's cache length (no launch of its own)
-        ok(L.ns_lm_layernorm_rows(h, C, self.lnf_w.data_ptr(), self.lnf_b.data_ptr(), a, C, B, C, eps, lens, st),
-           "ns_lm_layernorm_rows")
+        _check(L.ns_lm_layernorm_rows(h, C, self.lnf_w.data_ptr(), self.lnf_b.data_ptr(), a, C, B, C, eps, lens, st),
+               "ns_lm_layernorm_rows")
         epi = _lib.NS_LM_EPI_STORE_F32 if out.dtype == torch.float32 else _lib.NS_LM_EPI_STORE
-        gemm(a, C, self.head_t, None, row(out), out.stride(0), epi, self.ld, C)
+        gemm(a, C, self.head_t, None, out.data_ptr(), out.stride(0), epi, self.ld, C)
+        return out
 
     # ------------------------------------------------------------------ graph-capturable decode step
     def begin_static(self, logits_out: torch.Tensor) -> None:
@@ -767,10 +600,6 @@ class BatchedGPT2:
         if logits_out.shape != (self.kv.B, self.ld) or logits_out.dtype != self.logits_dtype:
             raise ValueError(f"static logits must be [{self.kv.B}, {self.ld}] {self.logits_dtype}")
         self._static_logits = logits_out
-
-    def static_capacity_left(self) -> int:
-        """Decode steps every slot can take within the pages it holds (graph replays cannot map pages)."""
-        return self.kv.steps_reserved(np.arange(self.kv.B))
 
     def reserve(self, steps: int) -> bool:
         """Lockstep callers: map the pages every slot needs for the next ``steps`` decode steps (False: the device
@@ -795,13 +624,16 @@ class BatchedGPT2:
         """Feed one token per stream (``[B]`` int); position = cache length mod n_positions.  ``live`` (host bool
         ``[B]``, native path): only these streams get pages and attention this step -- a lockstep caller whose
         streams end at different lengths (the span splitter's decodes) stops paying, in memory and reads, for the
-        finished ones; their logits rows are not meaningful afterwards."""
+        finished ones; their logits rows are not meaningful afterwards.  ``live`` is carried to the attention as this
+        step's ``stop_len``, so it cannot be combined with a caller's own ``stop_len`` (``ValueError``)."""
         B = self.B
         if tokens.shape != (B,):
             raise ValueError(f"expected {B} tokens")
         if self.native:
             from ..exceptions import KVCapacityError
 
+            if live is not None and self.stop_len is not None:
+                raise ValueError("step(live=...) would replace the stop_len that is set: use one of the two")
             if live is None:
                 ok = self.reserve(1)
             else:
@@ -810,14 +642,15 @@ class BatchedGPT2:
             if not ok:
                 raise KVCapacityError(f"KV cache full at {self.L} positions for B={B}: no device memory for a page")
             out = torch.empty((B, self.ld), device=self.device, dtype=self.logits_dtype)
-            saved = self.stop_len
-            if live is not None and not live.all():  # the attention skips a stream whose length reached its stop
+            if live is None or live.all():
+                self._decode_native(tokens, out)
+            else:  # the attention skips a stream whose length reached its stop
                 stop = np.where(live, np.iinfo(np.int32).max, 0).astype(np.int32)
                 self.stop_len = torch.from_numpy(stop).to(self.device)
-            try:
-                self._decode_native(tokens, out)
-            finally:
-                self.stop_len = saved
+                try:
+                    self._decode_native(tokens, out)
+                finally:
+                    self.stop_len = None
             self.advance(1)
             return out
         if self.L >= self.max_len:
@@ -830,26 +663,10 @@ class BatchedGPT2:
         return self._logits(h[:, -1])
 
 
-def _cu_masked_stream(device, frac: float, first: bool):
-    """A HIP stream whose kernels may run on a subset of the CUs (``hipExtStreamCreateWithCUMask``): the first
-    ``frac`` of every 8 consecutive CU ids (``first``) or the rest -- an even share of each XCD whatever way the ids
-    interleave the XCDs.  Eager launches only (a captured graph does not keep a stream's mask)."""
-    import ctypes
-
-    ncu = torch.cuda.get_device_properties(device).multi_processor_count
-    k = max(1, min(7, int(round(8 * float(frac)))))
-    bits = [((i % 8) < k) == first for i in range(ncu)]
-    words = (ctypes.c_uint32 * ((ncu + 31) // 32))()
-    for i, on in enumerate(bits):
-        if on:
-            words[i // 32] |= 1 << (i % 32)
-    hip = ctypes.CDLL("libamdhip64.so")
-    handle = ctypes.c_void_p()
-    with torch.cuda.device(device):
-        rc = hip.hipExtStreamCreateWithCUMask(ctypes.byref(handle), ctypes.c_uint32(len(words)), words)
+def _check(rc: int, what: str) -> None:
+    """Return code of a native library call: non-zero is an error (a refused argument or a failed launch)."""
     if rc != 0:
-        raise RuntimeError(f"hipExtStreamCreateWithCUMask failed ({rc})")
-    return torch.cuda.ExternalStream(handle.value, device=device)
+        raise RuntimeError(f"{what} failed ({rc})")
 
 
 def _normalise_device(dev: torch.device) -> torch.device:

@@ -238,7 +238,7 @@ def test_gpt2_fp16_decode_hip_attention_matches_sdpa_and_hf(B):
     m = random_gpt2("gpt2", seed=5)
     a = BatchedGPT2(m, device="cuda", compute_dtype=torch.float16)
     b = BatchedGPT2(m, device="cuda", compute_dtype=torch.float16)
-    b.native = b.hip_attention = False  # the PyTorch decode path (hipBLASLt GEMMs + SDPA) on the same weights
+    b.native = False  # the PyTorch decode path (hipBLASLt GEMMs + SDPA) on the same weights
     assert a.native
     ctx = synthetic.DEFAULT_CONTEXT
     la, lb = a.prefill(ctx, B, 4), b.prefill(ctx, B, 4)

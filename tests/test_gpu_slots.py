@@ -291,24 +291,23 @@ def test_history_and_table_growth_inside_the_pipelined_loop():
     assert max(map(len, ref)) > 64  # several growths of the 8-token start
 
 
-@pytest.mark.parametrize("order,cu_split", [("alternate", None), ("free", None), ("split", None), ("split", 0.5)])
-def test_two_decode_lanes_give_the_same_tokens(order, cu_split):
-    """The decode step as two row halves on two streams (``decode_lanes = 2``, one half's GEMMs beside the other's
-    attention): the same tokens as one launch chain -- graph-replayed with refilled slots and compaction, eager -- and
-    the decode round-trips through the lanes too."""
-    lm = _provider(seed=49)
-    ctx = [lm.vocab - 1] + list(synthetic.DEFAULT_CONTEXT[1:])
-    bits = [synthetic.bytes_to_bits_lsb(synthetic.payload_bytes(400 + s, n)) for s, n in
-            enumerate([24, 3, 40, 16, 1, 31, 24, 8, 48, 12, 20, 5, 33, 9, 17, 26, 2, 44, 11, 30])]
-    ref = lm.encode_batch(bits, ctx, quality=Q)
-    lm.lm.decode_lanes, lm.lm.decode_lanes_min_batch, lm.lm.decode_lanes_order = 2, 2, order
-    lm.lm.decode_lane_cu_split = cu_split
-    graphs = order != "split"  # the split form runs eagerly only
-    try:
-        assert lm.encode_batch(bits, ctx, quality=Q, graphs=graphs) == ref
-        assert lm.encode_batch(bits, ctx, quality=Q, slots=7, graphs=graphs) == ref
-        assert lm.encode_batch(bits, ctx, quality=Q, graphs=False) == ref
-        out = lm.decode_batch(ref, ctx, quality=Q, graphs=graphs)
-        assert all(o[: len(b)] == b for o, b in zip(out, bits))
-    finally:
-        lm.lm.decode_lanes = 1
+def test_step_live_refuses_a_callers_stop_len():
+    """``step(tokens, live=...)`` carries ``live`` to the attention as that step's ``stop_len``: with a caller's
+    ``stop_len`` set it raises on the host, before a page is mapped or a length advanced, instead of replacing it."""
+    from neuralsteganography_amd.lm.gpt2 import BatchedGPT2, random_gpt2
+
+    model = random_gpt2("tiny", n_layer=1, n_head=2, n_embd=128, vocab_size=512, n_positions=64)
+    lm = BatchedGPT2(model, device="cuda", compute_dtype=torch.float16)
+    assert lm.native
+    lm.prefill([5, 6, 7], 3, 8)
+    tokens = torch.tensor([1, 2, 3], device="cuda")
+    live = [True, False, True]
+    L0, lens0, pages0 = lm.L, lm.kv.lens.cpu().clone(), lm.kv.table.cpu().clone()
+    lm.stop_len = torch.full((3,), 100, dtype=torch.int32, device="cuda")
+    with pytest.raises(ValueError):
+        lm.step(tokens, live=live)
+    assert lm.L == L0 and torch.equal(lm.kv.lens.cpu(), lens0) and torch.equal(lm.kv.table.cpu(), pages0)
+    lm.stop_len = None
+    out = lm.step(tokens, live=live)
+    assert out.shape == (3, lm.ld) and lm.L == L0 + 1 and lm.stop_len is None
+    assert torch.isfinite(out[[0, 2], :512].float()).all()

@@ -173,7 +173,7 @@ def test_kv_cache_budget_keeps_headroom_and_retries_fragmented_segments(monkeypa
 
     calls, released = [], []
 
-    def fake_allocate(B_, max_len, T0=0, dtype=None, plain=None):
+    def fake_allocate(B_, max_len, T0=0):
         calls.append(max_len)
         if len(calls) == 1:
             raise torch.OutOfMemoryError("fragmented segments")

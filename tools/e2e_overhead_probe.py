@@ -23,6 +23,7 @@ def main():
     from neuralsteganography_amd import coder as coder_mod
     from neuralsteganography_amd import synthetic
     from neuralsteganography_amd.lm import arithmetic as A
+    from neuralsteganography_amd.lm import slots
     from neuralsteganography_amd.lm.gpt2 import random_gpt2
 
     B = args.batch
@@ -33,7 +34,6 @@ def main():
     bits = [synthetic.bytes_to_bits_lsb(synthetic.payload_bytes(s, args.bytes)) for s in range(B)]
     lm.encode_batch([b[:64] for b in bits], ctx, quality=q)
     lm.lm.prefill(ctx, B, 2 * max(len(b) for b in bits) + 64)  # as bench.py: the full-size cache once
-    lm.lm.k_cache = lm.lm.v_cache = None
     torch.cuda.synchronize()
     acc = {}
 
@@ -51,7 +51,7 @@ def main():
         setattr(obj, name, g)
 
     wrap(lm.lm, "prefill", "prefill")
-    wrap(A._StepGraph, "__init__", "first_step_and_capture")
+    wrap(slots._SlotGraph, "__init__", "first_step_and_capture")
     wrap(coder_mod.EncodeSession, "fields", "fields")
     marks = []
     f0 = coder_mod.EncodeSession.fields
