@@ -45,7 +45,8 @@ int ns_lm_gemm(const void* d_x, int64_t ldx, const void* d_wt, int64_t ldw, cons
                int64_t ldy, int M, int N, int K, int epilogue, void* hip_stream);
 
 /* ns_lm_gemm with a forced tile configuration 0 <= config < ns_lm_gemm_configs() (-1 = the automatic choice):
- * direct 16/32/64-row waves, 64x64 / 128x128 / 256x128 / 128x256 LDS tiles with 2-4 stages.  Every
+ * direct 16/32/64-row waves, 64x64 / 96x128 / 128x128 / 256x128 / 128x256 LDS tiles with 2-4 stages, persistent
+ * 128x128 tiles, 256x256 and 192x256 tiles with ping-pong or phase-pipelined wave groups (K <= 1024).  Every
  * configuration produces the same bits (the batch-invariance contract); the choice is speed only (tuning and
  * tests). */
 int ns_lm_gemm_config(const void* d_x, int64_t ldx, const void* d_wt, int64_t ldw, const void* d_bias, void* d_y,

@@ -125,6 +125,41 @@ __device__ __forceinline__ void store4_pre(void* Y, int64_t ldy, bool has_bias, 
     }
 }
 
+// Epilogue of a wave's FN x FM fragments (fragment (i, j): n = nb + 16 i + 4 fc, m = mb + 16 j + fr) through
+// store4_pre: the bias and every residual value are loaded together, one memory round trip for the whole tile
+// instead of two dependent ones per fragment.  Columns >= N and rows >= M are not touched.
+template <int EPI, int FN, int FM>
+__device__ __forceinline__ void store_frags(void* Y, int64_t ldy, const f16* __restrict__ bias, int M, int N, int nb,
+                                            int mb, int fr, int fc, const f32x4 (&acc)[FN][FM]) {
+    f16x4 bb[FN], h[EPI == NS_LM_EPI_RESIDUAL ? FN : 1][EPI == NS_LM_EPI_RESIDUAL ? FM : 1];
+#pragma unroll
+    for (int i = 0; i < FN; ++i) {
+        const int n = nb + i * 16 + 4 * fc;
+        bb[i] = f16x4{};
+        if (bias && n < N) bb[i] = *(const f16x4*)(bias + n);
+        if constexpr (EPI == NS_LM_EPI_RESIDUAL) {
+#pragma unroll
+            for (int j = 0; j < FM; ++j) {
+                const int m = mb + j * 16 + fr;
+                h[i][j] = f16x4{};
+                if (n < N && m < M) h[i][j] = *(const f16x4*)((const f16*)Y + (int64_t)m * ldy + n);
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < FN; ++i) {
+        const int n = nb + i * 16 + 4 * fc;
+        if (n >= N) continue;
+#pragma unroll
+        for (int j = 0; j < FM; ++j) {
+            const int m = mb + j * 16 + fr;
+            f16x4 hv = f16x4{};
+            if constexpr (EPI == NS_LM_EPI_RESIDUAL) hv = h[i][j];
+            if (m < M) store4_pre<EPI>(Y, ldy, bias != nullptr, bb[i], hv, m, n, acc[i][j]);
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------ canonical order
 // The K range is cut into SK = chains(K) consecutive chains of 64-wide tiles (SK = 1 up to K = 1024, 2 up to
 // 2048, else 4; tiles_per_chain = ceil(KT / SK)); each chain is ONE fp32 MFMA accumulation from zero, and the
@@ -381,16 +416,7 @@ __global__ __launch_bounds__(64 * WN * WM) void gemm_tiled(const f16* __restrict
                 for (int j = 0; j < FM; ++j) acc[i][j] = tot[i][j] + acc[i][j];
         }
     }
-#pragma unroll
-    for (int i = 0; i < FN; ++i) {
-        const int n = n0 + wn * FN * 16 + i * 16 + 4 * fc;
-        if (n >= N) continue;
-#pragma unroll
-        for (int j = 0; j < FM; ++j) {
-            const int m = m0 + wm * FM * 16 + j * 16 + fr;
-            if (m < M) store4<EPI>(Y, ldy, bias, m, n, acc[i][j]);
-        }
-    }
+    store_frags<EPI>(Y, ldy, bias, M, N, n0 + wn * FN * 16, m0 + wm * FM * 16, fr, fc, acc);
 }
 
 // ------------------------------------------------------------------------------------------------ persistent
@@ -833,6 +859,167 @@ __global__ __launch_bounds__(512) void gemm_pp(const f16* __restrict__ X, int64_
     }
 }
 
+// ---------------------------------------------------------------------------------------------------- phased
+// gemm_ph<EPI, BN>: the tile, wave layout and two staggered wave groups of gemm_pp, with the K-tile cut into four
+// phases and the copies counted instead of drained.  Phase p of a K-tile is one quarter of the wave's tile --
+// activation fragments j = 2p, 2p+1 against all FN weight fragments, both k-steps: 4 * FN MFMAs -- and is two
+// barrier slots long: an L slot (the phase's ds_reads: 4 activation fragments, in phase 0 also the 2 * FN weight
+// fragments; one staging unit of a LATER K-tile; in phases 1 and 3 a counted vmcnt) and an M slot (the MFMAs at
+// raised priority).  Group 1 runs one slot behind group 0, so on every SIMD one wave is in its M slot while the
+// other is in its L slot.
+// Staging: a K-tile is 4 units per thread -- u0 = weight rows 0..127, u1 = the other weight rows, u2 / u3 =
+// activation rows 0..63 / 64..127 of the wave's own group -- each piece 64 LDS rows over the 512 threads (weights)
+// or 32 rows over a group's 256 (activations).  Phase P (counted over all K-tiles) issues unit P + 6, so a K-tile's
+// units are issued in phases 2, 3 of the K-tile two before it and 0, 1 of the one before it.  Phase 3 waits until
+// u0..u2 of the next K-tile have landed (u3 and the two units issued since may stay in flight: vmcnt(NA)), phase 1
+// until u3 of this K-tile has (the next K-tile's four units stay in flight: vmcnt(NB)); in the last K-tile(s) the
+// units that no longer exist are left out of the counts.
+// Hazards, P counted in phases, group g in slot 2P + g: a unit waited for in phase P has landed for every issuing
+// wave at the barrier that ends slot 2P + 1, and is first read in phase P + 1 (slot >= 2P + 2).  A unit is copied
+// into LDS rows last read two or more phases before (weights: read in phase 0 of K-tile t, refilled from phase 2;
+// activation rows 0..63: read in phases 0 and 1, refilled in phase 0 of t + 1; rows 64..127: phases 2 and 3,
+// refilled in phase 1 of t + 1), and every L slot ends with lgkmcnt(0).  Every wave executes 8 * KT + 2 barriers
+// whatever M, N and KT.  One K chain (K <= 1024); ragged N / M clamped on load, not stored.
+template <int EPI, int BN = 256>
+__global__ __launch_bounds__(512) void gemm_ph(const f16* __restrict__ X, int64_t ldx, const f16* __restrict__ Wt,
+                                               int64_t ldw, const f16* __restrict__ bias, void* Y, int64_t ldy, int M,
+                                               int N, int K) {
+    static_assert(BN == 256 || BN == 192, "weight panel");
+    constexpr int BM = 256, FN = BN / 64, FM = 8, SB = (BN + BM) * 128;
+    constexpr int WP = BN / 64;                                 // weight pieces per thread and K-tile
+    constexpr int SZ0 = 2, SZ1 = WP - 2, SZ2 = 2, SZ3 = 2;      // pieces per unit
+    constexpr int NA = SZ3 + SZ0 + SZ1, NB = SZ0 + SZ1 + SZ2 + SZ3;
+    __shared__ __attribute__((aligned(16))) char smem[2 * SB];
+
+    const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
+    const int t = xcd_remap(blockIdx.x, tiles_m * tiles_n);
+    constexpr int GN = 4;
+    const int grp = t / (GN * tiles_m), within = t - grp * (GN * tiles_m);
+    const int gn = min(GN, tiles_n - grp * GN);
+    const int tm = within / gn, tn = grp * GN + (within - tm * gn);
+    const int n0 = tn * BN, m0 = tm * BM;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int g = wave >> 2, wn = wave & 3;
+    const int fr = lane & 15, fc = lane >> 4;
+    const int lr = lane >> 3;
+    // every piece of a wave starts at an LDS row = 8 * wn mod 16, so one swizzle chunk serves them all
+    const int chunk = (lane & 7) ^ ((wn * 4 + (lane >> 4)) & 7);
+    const f16* pw[WP];  // weight piece q: LDS rows q * 64 + wave * 8 + lr
+    const f16* px[4];   // activation piece q: LDS rows BN + g * 128 + q * 32 + wn * 8 + lr
+#pragma unroll
+    for (int q = 0; q < WP; ++q) pw[q] = Wt + (int64_t)min(n0 + q * 64 + wave * 8 + lr, N - 1) * ldw + chunk * 8;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        px[q] = X + (int64_t)min(m0 + g * 128 + q * 32 + wn * 8 + lr, M - 1) * ldx + chunk * 8;
+    auto piece_w = [&](int q, int kt, int buf) {
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(pw[q] + kt * BK),
+                                         (__attribute__((address_space(3))) void*)(smem + buf * SB +
+                                                                                   (q * 64 + wave * 8) * 128),
+                                         16, 0, 0);
+    };
+    auto piece_x = [&](int q, int kt, int buf) {
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(px[q] + kt * BK),
+                                         (__attribute__((address_space(3))) void*)(smem + buf * SB +
+                                                                                   (BN + g * 128 + q * 32 + wn * 8) * 128),
+                                         16, 0, 0);
+    };
+    auto unit = [&](int u, int kt, int buf) {
+        if (u == 0) {
+            piece_w(0, kt, buf);
+            piece_w(1, kt, buf);
+        } else if (u == 1) {
+#pragma unroll
+            for (int q = 2; q < WP; ++q) piece_w(q, kt, buf);
+        } else {
+            piece_x(2 * (u - 2), kt, buf);
+            piece_x(2 * (u - 2) + 1, kt, buf);
+        }
+    };
+    auto barrier = []() {
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+    };
+
+    f32x4 acc[FN][FM];
+#pragma unroll
+    for (int i = 0; i < FN; ++i)
+#pragma unroll
+        for (int j = 0; j < FM; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    const int KT = K / BK;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) unit(u, 0, 0);
+    if (KT > 1) {
+        unit(0, 1, 1);
+        unit(1, 1, 1);
+        wait_vm<NA>();
+    } else {
+        wait_vm<SZ3>();
+    }
+    barrier();
+    if (g == 1) barrier();  // group 1 starts one slot late
+    for (int kt = 0; kt < KT; ++kt) {
+        const int buf = kt & 1;
+        const char* base = smem + buf * SB;
+        f16x8 a[2][FN];
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            // ---- L slot
+            f16x8 b[2][2];
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk) {
+                const int ch = kk * 4 + fc;
+                if (p == 0) {
+#pragma unroll
+                    for (int i = 0; i < FN; ++i) {
+                        const int row = wn * FN * 16 + i * 16 + fr;
+                        a[kk][i] = *(const f16x8*)(base + row * 128 + ((ch ^ swz(row)) << 4));
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const int row = BN + g * FM * 16 + (2 * p + j) * 16 + fr;
+                    b[kk][j] = *(const f16x8*)(base + row * 128 + ((ch ^ swz(row)) << 4));
+                }
+            }
+            if (p < 2) {
+                if (kt + 1 < KT) unit(p + 2, kt + 1, buf ^ 1);
+            } else {
+                if (kt + 2 < KT) unit(p - 2, kt + 2, buf);
+            }
+            if (p == 1) {
+                if (kt + 1 < KT)
+                    wait_vm<NB>();
+                else
+                    wait_vm<0>();
+            }
+            if (p == 3) {
+                if (kt + 2 < KT)
+                    wait_vm<NA>();
+                else if (kt + 1 < KT)
+                    wait_vm<SZ3>();
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            barrier();
+            // ---- M slot
+            __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+                for (int i = 0; i < FN; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) acc[i][2 * p + j] = mfma16(a[kk][i], b[kk][j], acc[i][2 * p + j]);
+            __builtin_amdgcn_s_setprio(0);
+            barrier();
+        }
+    }
+    if (g == 0) barrier();  // same barrier count for both groups
+    store_frags<EPI>(Y, ldy, bias, M, N, n0 + wn * FN * 16, m0 + g * FM * 16, fr, fc, acc);
+}
+
 // ------------------------------------------------------------------------------------------------ chains
 // gemm_chains<SK, EPI> (round 5): the SK = k_chains(K) = 2 or 4 K chains of the canonical order computed side by
 // side instead of one after the other.  A workgroup of 4 * SK waves owns one 64 x 64 tile; wave group c (4 waves of
@@ -1176,6 +1363,8 @@ enum GemmCfg {
     CFG_PP256,                                        // 256 x 256, two ping-pong wave groups (K <= 1024)
     CFG_PP192,                                        // 192 weight rows x 256, the same ping-pong kernel
     CFG_C64,                                          // 64 x 64, the K chains side by side (K > 1024; round 5)
+    CFG_T96x128_3, CFG_T96x128_4,                     // 96 weight rows x 128, 4 waves of 48 x 64, 3 / 4 stages
+    CFG_PH256, CFG_PH192,                             // 256 / 192 x 256, phase-pipelined wave groups (K <= 1024)
     CFG_COUNT
 };
 
@@ -1275,6 +1464,24 @@ static void launch_cfg(int cfg, const f16* x, int64_t ldx, const f16* wt, int64_
                                    ldy, M, N, K);
             }
             break;
+        case CFG_T96x128_3: NSG_TILED(96, 128, 2, 2, 3); break;
+        case CFG_T96x128_4: NSG_TILED(96, 128, 2, 2, 4); break;
+        case CFG_PH256:
+            if (split) {
+                NSG_TILED(128, 128, 2, 2, 2);
+            } else {
+                hipLaunchKernelGGL((gemm_ph<EPI>), tiles(256, 256), dim3(512), 0, st, x, ldx, wt, ldw, bias, y, ldy, M,
+                                   N, K);
+            }
+            break;
+        case CFG_PH192:
+            if (split) {
+                NSG_TILED(128, 128, 2, 2, 2);
+            } else {
+                hipLaunchKernelGGL((gemm_ph<EPI, 192>), tiles(192, 256), dim3(512), 0, st, x, ldx, wt, ldw, bias, y,
+                                   ldy, M, N, K);
+            }
+            break;
         case CFG_C64: {
             const int sk = k_chains(K);
             if (sk == 4)
@@ -1324,23 +1531,27 @@ static void launch_cfg(int cfg, const f16* x, int64_t ldx, const f16* wt, int64_
 // Automatic choice by shape (speed only: every configuration gives the same bits).  From the per-config sweep
 // at M = 16 ... 4096 on GPT-2 shapes (profiles/lmprobe_r02j_*.jsonl): 64 x 64 LDS tiles for the short-K GEMMs
 // from M = 16 up; direct waves for the long-K (split) GEMM up to M = 256, where spreading the chains over
-// waves beats tiling; 128 x 128 tiles only for the vocabulary-wide head at large M.
+// waves beats tiling; 128 x 128 tiles for the vocabulary-wide head at large M, and 192 / 256 x 256 phase-pipelined
+// tiles for the wide one-chain GEMMs at B >= 4096.
 static int auto_cfg(int M, int N, int K) {
     const bool split = k_chains(K) > 1;
     if (M <= 16) return (N >= 8192 && !split) ? CFG_T64_2 : CFG_DIRECT16;
     if (split && M <= 256) return M <= 64 ? CFG_DIRECT16 : M <= 128 ? CFG_DIRECT32 : CFG_DIRECT64;
     // the vocabulary-wide head: 256 x 256 ping-pong tiles below B = 2048 (GPT-2-medium B = 1024: 786 vs 740
-    // TFLOP/s), 128 x 128 above (B = 4096: 752 vs 726; profiles/r04/lmprobe_r04aa_*.jsonl)
+    // TFLOP/s), 128 x 128 above (B = 4096: 752 vs 726; profiles/r04/lmprobe_r04aa_*.jsonl).  The phase-pipelined
+    // 256 x 256 kernel wins the back-to-back probe at B = 4096 (758 vs 738) but not the decode step itself: 423 vs
+    // 387 us per launch, 5.189 vs 5.169 ms per step, same machine, alternating runs -- the head keeps its choice.
     if (N >= 8192 && M >= 512) return (!split && M < 2048) ? CFG_PP256 : CFG_T128_2;
-    // B >= 4096, K <= 1024, wide N: the ping-pong kernel, with 192- or 256-wide weight panels, whichever needs fewer
-    // panel-rows of work per CU (GPT-2's c_fc: 256 tiles of 192 = one per CU, 644 vs 579 TFLOP/s for 192 tiles of
-    // 256; c_attn 556 vs 487 on 64 x 64 tiles; profiles/r04/lmprobe_r04ag_*.jsonl).  GPT-2-medium's c_fc (N = 4096)
-    // at B = 1024 on 128 x 64 tiles (506 vs 471); the other shapes and smaller batches stay on 64 x 64 tiles.
+    // B >= 4096, K <= 1024, wide N: the phase-pipelined kernel with 192- or 256-wide weight panels, whichever needs
+    // fewer panel-rows of work per CU (GPT-2's c_fc: 256 tiles of 192 = one per CU, 683 vs 636 TFLOP/s on the
+    // ping-pong kernel at the same tile; c_attn 610 vs 570; profiles/r07/lmprobe_r07_*.jsonl).  GPT-2-medium's c_fc
+    // (N = 4096) at B = 1024 on 128 x 64 tiles (543 vs 510); the other shapes and smaller batches stay on 64 x 64 tiles
+    // (the 96 x 128 tiles, one per CU at N = 768, measured 380 vs 427 and 488 vs 547 there).
     if (!split && M >= 4096 && N >= 2048) {
         const long cu = cu_count(), tm = (M + 255) / 256;
         const long w256 = (tm * ((N + 255) / 256) + cu - 1) / cu * 256;
         const long w192 = (tm * ((N + 191) / 192) + cu - 1) / cu * 192;
-        return w192 < w256 ? CFG_PP192 : CFG_PP256;
+        return w192 < w256 ? CFG_PH192 : CFG_PH256;
     }
     if (!split && M >= 1024 && N >= 4096) return CFG_T128x64_3;
     // long K (two or four chains) with few 64 x 64 tiles: the chains side by side (GPT-2-medium's mlp c_proj at
