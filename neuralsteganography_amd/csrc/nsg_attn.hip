@@ -431,6 +431,11 @@ __global__ __launch_bounds__(512) void decode_attn_kernel(const _Float16* __rest
 // merges pair j's S partials in split order with the lockstep kernel's arithmetic (an S = 1 "merge" is exact: *1,
 // +0).  Same rows, same order, same operations: the output bits equal the lockstep kernel's for the same cache
 // contents, and still depend on a pair's own key count only (batch-invariant).
+//
+// Short keys (8-pair workgroups whose pairs are all one wave, a context of at least one whole chunk, no window cutting
+// it -- the first 224 steps of every job from a 32-token context): a short path (NSG_ATT_SHORT) with the same
+// arithmetic per pair but the context chunk, q and the lengths requested at kernel entry, wave w serving slot w, and
+// no loads for rows at or past the new token.  DESIGN §4d, library 0.27.
 struct PagedArgs {
     const _Float16* qkv;
     int64_t qkv_stride;
@@ -484,6 +489,99 @@ __device__ __forceinline__ uint64_t readlane64(uint64_t v, int lane) {  // lane 
     return ((uint64_t)hi << 32) | lo;
 }
 
+#ifndef NSG_ATT_SHORT
+#define NSG_ATT_SHORT 1  // paged kernel, 8-pair workgroups: the short-key path (below); 0 = the general path only,
+                         // 2 = the short path with the general path's clamped loads in the boundary iterations (A/B)
+#endif
+
+// One 32-row iteration of a pair's online softmax: the rows' scores, the running maximum, the rescale and the P.V
+// accumulation.  row0 = the position of this lane's row in the first RPI-row slab.  GEN: rows past L0 are masked
+// out and row L0 is the new token (knew / vnew, from registers); otherwise every row is a cached one.
+// These three helpers are the short-key path's; they restate the task loop's math_chunk, row-group merge and store
+// operation for operation (the bits are compared on every stream, tests/test_gpu_paged_short.py).  The task loop
+// keeps its own text: routed through the helpers, the P = 1 kernels no longer compiled to the same instructions.
+template <class F, bool GEN>
+__device__ __forceinline__ void paged_chunk_math(const typename F::Q& q, typename F::Raw (&kr)[F::NI],
+                                                 typename F::Raw (&vr)[F::NI], int row0, int L0,
+                                                 const typename F::Raw& knew, const typename F::Raw& vnew,
+                                                 float scale_log2, float& m, float& l, float (&acc)[F::DPL]) {
+    constexpr int DPL = F::DPL, LPR = F::LPR, RPI = F::RPI, NI = F::NI;
+    float sc[NI];
+    bool valid[NI];
+    float mx = m;
+#pragma unroll
+    for (int u = 0; u < NI; ++u) {
+        const int row = row0 + RPI * u;
+        valid[u] = GEN ? row <= L0 : true;
+        if (GEN && row == L0) {
+            kr[u] = knew;
+            vr[u] = vnew;
+        }
+        float sv = F::dot(q, kr[u]);
+        if constexpr (NSG_ATT_DPP) {
+            sv = row_group_sum<LPR>(sv);
+        } else {
+#pragma unroll
+            for (int off = 1; off < LPR; off <<= 1) sv += __shfl_xor(sv, off);
+        }
+        sc[u] = sv * scale_log2;
+        if (valid[u]) mx = fmaxf(mx, sc[u]);
+    }
+    const float alpha = exp2f(m - mx);
+    l *= alpha;
+#pragma unroll
+    for (int d = 0; d < DPL; ++d) acc[d] *= alpha;
+#pragma unroll
+    for (int u = 0; u < NI; ++u) {
+        const float p = valid[u] ? exp2f(sc[u] - mx) : 0.0f;
+        l += p;
+        float v[DPL];
+        F::unpack(vr[u], v);
+#pragma unroll
+        for (int d = 0; d < DPL; ++d) acc[d] = fmaf(p, v[d], acc[d]);
+    }
+    m = mx;
+}
+
+// merge the row groups (lanes c, c + LPR, ... hold the same dims); the lane ^ 8 step as a DPP row_ror:8 (within a
+// 16-lane row that IS lane ^ 8; the merge is symmetric in the two lanes, so the same bits), the others through
+// ds_bpermute
+template <class F>
+__device__ __forceinline__ void paged_merge_groups(float& m, float& l, float (&acc)[F::DPL]) {
+#pragma unroll
+    for (int off = F::LPR; off < 64; off <<= 1) {
+        const bool dpp8 = NSG_ATT_DPP && off == 8;
+        const float mo = dpp8 ? row_ror8(m) : __shfl_xor(m, off);
+        const float lo = dpp8 ? row_ror8(l) : __shfl_xor(l, off);
+        const float mn = fmaxf(m, mo);
+        const float fa = exp2f(m - mn), fo = exp2f(mo - mn);
+        l = l * fa + lo * fo;
+#pragma unroll
+        for (int d = 0; d < F::DPL; ++d) {
+            const float ao = dpp8 ? row_ror8(acc[d]) : __shfl_xor(acc[d], off);
+            acc[d] = acc[d] * fa + ao * fo;
+        }
+        m = mn;
+    }
+}
+
+// out = acc / l: this lane's DPL dims from o (the pair's output row + the lane's first dim)
+template <class F>
+__device__ __forceinline__ void paged_store_out(_Float16* o, float l, const float (&acc)[F::DPL]) {
+    const float inv = 1.0f / l;
+#pragma unroll
+    for (int h8 = 0; h8 < F::DPL / 8; ++h8) {
+        f16x8 r;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            float tv = acc[h8 * 8 + i] * inv;
+            asm volatile("" : "+v"(tv));
+            r[i] = (_Float16)tv;
+        }
+        *(f16x8*)(o + h8 * 8) = r;
+    }
+}
+
 template <class F, int P>
 constexpr int paged_waves_per_eu() {  // NSG_ATT_DB8 fp8: room for the second chunk's registers
     return P == 1 ? 1 : (NSG_ATT_DB8 && std::is_same<F, FmtF8>::value) ? NSG_ATT_DB8_WPE : 4;
@@ -506,12 +604,51 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(paged_waves
     // the same few loads in every wave hit the caches) -- no barrier before the streaming starts; the wave keeps
     // them in its own LDS slots, not in registers.
     int pr = -1, pL0 = 0, ps0 = 0, pS = 0, pst = 0;  // status 0 none / skipped, 1 run, 2 poison
+    // Short-key path (8 streams of one head per workgroup, context of at least one whole chunk): everything that
+    // depends on the workgroup and the lane alone is requested at kernel entry, in one round trip -- the lengths
+    // and skip flags first, then the q row of the stream in slot (wave) and the context's first 32 K/V rows of the
+    // workgroup's head.  The context rows are shared by the workgroup's 8 waves and by the other workgroups of the
+    // head: default cache policy, not non-temporal.  A workgroup that then leaves the short path (a split pair, a
+    // window cutting the first chunk) drops these registers; the loads are always legal (T0 >= 32 context rows, a
+    // stream index clamped into the batch).
+    constexpr bool SHORTP = P == 8 && NSG_ATT_HEAD_MAJOR && NSG_ATT_SHORT;
+    const bool ctx32 = SHORTP && a.T0 >= RPI * NI;  // uniform over the launch
+    int eL0 = 0, estop = 0;
+    uint32_t edone = 0;
+    typename F::Q q0 = {};
+    Raw ck[NI] = {}, cv[NI] = {};
+    if constexpr (SHORTP) {
+        {  // every lane asks for the words of slot (lane % P), stream index clamped into the batch: no branch, so
+           // nothing waits between these requests and the ones below
+            const int bs = min((int)(blockIdx.x / a.H) * P + lane % P, a.B - 1);
+            eL0 = a.lens[bs];
+            // (absent flags or stops: any readable word, lens[0]; the value is not used)
+            edone = *(a.done ? a.done + (int64_t)bs * a.done_stride : (const uint32_t*)a.lens);
+            estop = *(a.stop ? a.stop + bs : a.lens);
+        }
+        if (ctx32) {
+            const int h = blockIdx.x % a.H, b = min((int)(blockIdx.x / a.H) * P + wave, a.B - 1);
+            const int64_t o = (int64_t)h * a.ph + (lane % LPR) * DPL + (lane / LPR) * ATT_D;  // row (lane / LPR)
+            q0 = F::load_q(a.qkv + (int64_t)b * a.qkv_stride + h * ATT_D + (lane % LPR) * DPL);
+#pragma unroll
+            for (int u = 0; u < NI; ++u) {
+                ck[u] = *((const Raw*)((const E*)a.kp + o + RPI * u * ATT_D));
+                cv[u] = *((const Raw*)((const E*)a.vp + o + RPI * u * ATT_D));
+            }
+        }
+    }
     if (lane < P) {
         pr = att_pair<P>(blockIdx.x, lane, a.B, a.H);
         if (pr >= 0) {
             const int b = pr / a.H;
-            pL0 = a.lens[b];
-            const bool skip = (a.done && (a.done[(int64_t)b * a.done_stride] & 1u)) || (a.stop && pL0 >= a.stop[b]);
+            bool skip;
+            if constexpr (SHORTP) {
+                pL0 = eL0;
+                skip = (a.done && (edone & 1u)) || (a.stop && pL0 >= estop);
+            } else {
+                pL0 = a.lens[b];
+                skip = (a.done && (a.done[(int64_t)b * a.done_stride] & 1u)) || (a.stop && pL0 >= a.stop[b]);
+            }
             if (!skip) {
                 // the new token's stream row: its page must exist (host invariant).  One pair per workgroup (P = 1,
                 // small batches): checked here, once; multi-pair workgroups: only the row is checked here and the page
@@ -532,6 +669,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(paged_waves
             }
         }
     }
+    const int g = lane / LPR;  // row within an RPI-row slab
+    const int c = lane % LPR;  // DPL-dim slice
+    const int C = a.H * ATT_D;
     int pfirst = 0, ntask = 0, multi = 0;  // task index of pair (lane)'s split 0; tasks; any pair split S > 1
 #pragma unroll
     for (int k = 0; k < P; ++k) {
@@ -540,9 +680,108 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(paged_waves
         ntask += sk;
         multi |= sk > 1;
     }
+    int cut = 0;  // any pair whose window starts past position 0 (its first chunk is not the context's)
+    if constexpr (SHORTP) {
+#pragma unroll
+        for (int k = 0; k < P; ++k) cut |= __shfl(ps0, k);
+    }
     if (wave < P && __shfl(pst, wave) == 2) {  // poisoned pair: NaN rows
         const int pair = __shfl(pr, wave);
         a.out[(int64_t)(pair / a.H) * a.out_stride + (pair % a.H) * ATT_D + lane] = (_Float16)__builtin_nanf("");
+    }
+    if constexpr (SHORTP) {
+        // Short-key path: no pair of the workgroup is split (every key count <= NSG_ATT_ROWS1, one wave per pair) and
+        // every pair's keys start at position 0, so iteration 0 is the context's first chunk, already in registers.
+        // Wave w serves the pair of slot w (a skipped or absent slot's wave retires at once).  The pair's arithmetic
+        // is the general path's: rows 0..L0 in order, 32-row iterations, the same online-softmax update, row-group
+        // merge and acc / l store -- only addresses, cache policy, load timing and never-used loads differ.
+        if (ctx32 && !multi && !cut) {  // uniform over the workgroup
+            const int w = __builtin_amdgcn_readfirstlane(wave);
+            if (__builtin_amdgcn_readlane(pst, w) != 1) return;  // none, skipped, or poisoned (NaN row written above)
+            const int pair = __builtin_amdgcn_readlane(pr, w);
+            const int L0 = __builtin_amdgcn_readlane(pL0, w);
+            const int T0 = a.T0;
+            const int b = pair / a.H, h = pair - b * a.H;
+            // the stream's page addresses, chunk i in lane i: chunks 0..cN hold stream rows 0..L0 - T0 (mapped
+            // through the new token's chunk: host invariant; cN < max_chunks was checked above, cN <= 7 as the key
+            // count is at most NSG_ATT_ROWS1).  One load, second and last round trip before the own rows.
+            const int cN = (L0 - T0) >> 5;
+            const uint64_t pgv = lane <= cN ? a.table[(int64_t)b * a.tstride + lane] : 0;
+            float m = -1e30f, l = 0.0f;
+            float acc[DPL];
+#pragma unroll
+            for (int d = 0; d < DPL; ++d) acc[d] = 0.0f;
+            // iteration 0: context rows 0..31 (< T0 <= L0: all valid, none the new token), while the table is in flight
+            paged_chunk_math<F, false>(q0, ck, cv, g, L0, ck[0], cv[0], a.scale_log2, m, l, acc);
+            const uint64_t apage = readlane64(pgv, cN);  // the new token's page; a missing one poisons the pair
+            const bool bad = apage == 0 || (apage & 15u);
+            const _Float16* qrow = a.qkv + (int64_t)b * a.qkv_stride + h * ATT_D + c * DPL;
+            const int64_t hoff = a.layer_off + (int64_t)h * 32 * ATT_D + c * DPL;  // this layer's K rows of head h
+            const E* kpb = (const E*)a.kp + (int64_t)h * a.ph + c * DPL;
+            const E* vpb = (const E*)a.vp + (int64_t)h * a.ph + c * DPL;
+            Raw knew = {}, vnew = {};
+            constexpr bool CLAMP = NSG_ATT_SHORT == 2;  // A/B: rows at or past L0 load a copy of row L0 - 1
+            for (int j0 = RPI * NI; j0 <= L0 && !bad; j0 += RPI * NI) {
+                const int jj0 = j0 - T0;
+                // the chunk of the first stream row the iteration loads; the last one is in ca or ca + 1 (<= 7)
+                const int ca = max(CLAMP ? min(jj0, L0 - 1 - T0) : jj0, 0) >> 5;
+                const E* pa = (const E*)readlane64(pgv, ca) + hoff;
+                const E* pb = (const E*)readlane64(pgv, ca + 1) + hoff;
+                if (jj0 >= 0 && j0 + RPI * NI <= L0) {  // interior: stream rows < L0 only
+#pragma unroll
+                    for (int u = 0; u < NI; ++u) {
+                        const int jj = jj0 + RPI * u + g;
+                        const E* ka = ((jj >> 5) == ca ? pa : pb) + (int64_t)(jj & 31) * ATT_D;
+                        ck[u] = att_load((const Raw*)ka);
+                        cv[u] = att_load((const Raw*)(ka + a.v_off));
+                    }
+                    paged_chunk_math<F, false>(q0, ck, cv, j0 + g, L0, knew, vnew, a.scale_log2, m, l, acc);
+                    continue;
+                }
+                // Boundary iteration (context rows past the first chunk, the new token, rows past it).  Only rows
+                // < L0 are loaded: row L0 is the new token, from the qkv row (requested here, with the last chunk, so
+                // it holds no registers during the stream), and a row past L0 keeps the bit pattern 0 = +0.0 in
+                // either format.  The general path feeds such a row a copy of row L0 - 1 instead; the bits cannot
+                // differ: the row is masked (valid = false), so its score never reaches the maximum, p = 0,
+                // l + 0 = l, and acc -- which starts at +0 and, sums under round-to-nearest never giving -0 unless
+                // both terms are -0, is never -0 -- takes fmaf(0, finite, acc) = acc for either value.  No register
+                // reaches the arithmetic uninitialised.
+                const bool lastit = j0 + RPI * NI > L0;
+                if (lastit) {
+                    knew = F::from_qkv(qrow + C);
+                    vnew = F::from_qkv(qrow + 2 * C);
+                }
+#pragma unroll
+                for (int u = 0; u < NI; ++u) {
+                    const int row = CLAMP ? min(j0 + RPI * u + g, L0 - 1) : j0 + RPI * u + g;
+                    ck[u] = Raw{};
+                    cv[u] = Raw{};
+                    if (row < T0) {  // shared by the head's workgroups: default policy
+                        ck[u] = *(const Raw*)(kpb + (int64_t)row * ATT_D);
+                        cv[u] = *(const Raw*)(vpb + (int64_t)row * ATT_D);
+                    } else if (row < L0) {
+                        const int jj = row - T0;
+                        const E* ka = ((jj >> 5) == ca ? pa : pb) + (int64_t)(jj & 31) * ATT_D;
+                        ck[u] = att_load((const Raw*)ka);
+                        cv[u] = att_load((const Raw*)(ka + a.v_off));
+                    }
+                }
+                paged_chunk_math<F, true>(q0, ck, cv, j0 + g, L0, knew, vnew, a.scale_log2, m, l, acc);
+                if (lastit && g == 0) {  // KV append of the new token (position L0)
+                    E* kd = (E*)apage + hoff + (int64_t)((L0 - T0) & 31) * ATT_D;
+                    *(Raw*)kd = knew;
+                    *(Raw*)(kd + a.v_off) = vnew;
+                }
+            }
+            paged_merge_groups<F>(m, l, acc);
+            if (bad) {
+                l = __builtin_nanf("");
+#pragma unroll
+                for (int d = 0; d < DPL; ++d) acc[d] = __builtin_nanf("");
+            }
+            if (g == 0) paged_store_out<F>(a.out + (int64_t)b * a.out_stride + h * ATT_D + c * DPL, l, acc);
+            return;
+        }
     }
     if (lane < P) {
         s_pi[wave][lane][0] = pr;
@@ -553,9 +792,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(paged_waves
     const int myS = wave < P ? __shfl(pS, wave) : 0;  // the merge phase's pair (wave) split
     __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the wave's own LDS slots are written before they are read
     __builtin_amdgcn_wave_barrier();
-    const int g = lane / LPR;  // row within an RPI-row slab
-    const int c = lane % LPR;  // DPL-dim slice
-    const int C = a.H * ATT_D;
     for (int t = wave; t < ntask; t += 8) {  // wave-uniform
         int j = 0;
 #pragma unroll
