@@ -1020,6 +1020,152 @@ __global__ __launch_bounds__(512) void gemm_ph(const f16* __restrict__ X, int64_
     store_frags<EPI>(Y, ldy, bias, M, N, n0 + wn * FN * 16, m0 + g * FM * 16, fr, fc, acc);
 }
 
+// ------------------------------------------------------------------------------------------- phased, 96 x 128
+// gemm_ph96<EPI, SPLIT>: 96 weight rows x 128 activation rows per workgroup of 8 waves -- GPT-2's two N = 768
+// projections at B = 4,096 are 8 x 32 = 256 such tiles, one per CU.  The 64 x 64 tiles these shapes ran on copy
+// every activation byte into LDS 12 times and every weight byte 64 times and sit on the rate at which a CU pulls
+// L2 lines into LDS; this tile moves (1 / 96 + 1 / 128) instead of 1 / 32 of M N K 2 bytes.
+// All eight waves read ONE staged K-tile, (96 + 128) rows x 128 B = 28 KiB, from a ring of four: rows 0..95 the
+// weights, 96..223 the activations, the logical 16-byte chunk c of row r at physical chunk c ^ swz(r).  Staging:
+// the K-tile is 28 pieces of 8 rows (one LDS-DMA instruction of a wave each); instruction i = 0..2 of wave w copies
+// piece 8 i + w, instruction 3 -- waves 0..3 only -- piece 24 + w: group 0 issues NI = 4 per K-tile, group 1 three.
+// Waves: group g = wave / 4 owns activation rows 64 g .. 64 g + 63, and in it wave (wn, wm) the 48 x 32 sub-tile
+// at weight row 48 wn, activation row 32 wm (FN = 3, FM = 2: 10 ds_read_b128 for 12 MFMAs per K-tile; 96 x 16 per
+// wave would need 14, and 24 weight rows are no multiple of the fragment).
+// A K-tile is two barrier slots per wave: an L slot (its 10 fragment reads; the copies of K-tile t + 3 into the
+// buffer of t - 1; a counted vmcnt that leaves the copies of t + 2 and t + 3 in flight, i.e. K-tile t + 1 has
+// landed; lgkmcnt(0)) and an M slot (the 12 MFMAs at raised priority).  Group 1 runs one slot behind group 0.
+// Hazards, group g in slot 2 t + g: K-tile t + 1 is waited for in slots 2 t (group 0) and 2 t + 1 (group 1), both
+// before the barrier that ends slot 2 t + 1, and first read in slot 2 t + 2.  K-tile t + 3 is copied from slot 2 t
+// on into the buffer last read in slots 2 t - 2 and 2 t - 1, which both ended with lgkmcnt(0) and a barrier.
+// Every wave executes 2 KT + 2 barriers whatever M, N and K.  The K chains run one after the other exactly as in
+// gemm_tiled's SPLIT form; ragged N / M are clamped on load and not stored.
+// Measured and not kept (library 0.28): a ring of five; the copies issued ahead of the fragment reads, or
+// half or all of them in the M slot between the MFMAs -- none faster, most 4-6 us slower on mlp c_proj.
+template <int EPI, bool SPLIT>
+__global__ __launch_bounds__(512) void gemm_ph96(const f16* __restrict__ X, int64_t ldx, const f16* __restrict__ Wt,
+                                                 int64_t ldw, const f16* __restrict__ bias, void* Y, int64_t ldy,
+                                                 int M, int N, int K) {
+    constexpr int BN = 96, BM = 128, FN = 3, FM = 2, NST = 4, SB = (BN + BM) * 128;
+    __shared__ __attribute__((aligned(16))) char smem[NST * SB];
+
+    const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
+    const int t = xcd_remap(blockIdx.x, tiles_m * tiles_n);
+    constexpr int GN = 1024 / BN;  // gemm_tiled's grouped order
+    const int grp = t / (GN * tiles_m), within = t - grp * (GN * tiles_m);
+    const int gn = min(GN, tiles_n - grp * GN);
+    const int tm = within / gn, tn = grp * GN + (within - tm * gn);
+    const int n0 = tn * BN, m0 = tm * BM;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int g = wave >> 2, wn = (wave >> 1) & 1, wm = wave & 1;
+    const int fr = lane & 15, fc = lane >> 4;
+    const int lr = lane >> 3;
+    // piece q starts at LDS row 8 q, and q = wave mod 8 for every piece of a wave: one swizzle chunk serves them all
+    const int chunk = (lane & 7) ^ (((wave & 1) * 4 + (lane >> 4)) & 7);
+    const f16* ps[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int row = min(i * 8 + wave, (BN + BM) / 8 - 1) * 8 + lr;  // (instruction 3 of group 1 is never issued)
+        ps[i] = (row < BN ? Wt + (int64_t)min(n0 + row, N - 1) * ldw : X + (int64_t)min(m0 + row - BN, M - 1) * ldx) +
+                chunk * 8;
+    }
+    auto stage = [&](int kt, int buf) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (i == 3 && g != 0) break;
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(ps[i] + kt * BK),
+                                             (__attribute__((address_space(3))) void*)(smem + buf * SB +
+                                                                                       (i * 8 + wave) * 1024),
+                                             16, 0, 0);
+        }
+    };
+    // wait until at most `tiles` K-tiles of this wave's copies (NI = 4 / 3 instructions each) are in flight
+    auto wait_tiles = [&](int tiles) {
+        if (g == 0) {
+            if (tiles >= 2) wait_vm<8>(); else if (tiles == 1) wait_vm<4>(); else wait_vm<0>();
+        } else {
+            if (tiles >= 2) wait_vm<6>(); else if (tiles == 1) wait_vm<3>(); else wait_vm<0>();
+        }
+    };
+    auto barrier = []() {
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+    };
+
+    f32x4 acc[FN][FM];
+    f32x4 tot[SPLIT ? FN : 1][SPLIT ? FM : 1];  // sum of the finished chains (canonical order)
+#pragma unroll
+    for (int i = 0; i < FN; ++i)
+#pragma unroll
+        for (int j = 0; j < FM; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    const int KT = K / BK;
+    const int SK = k_chains(K), TPC = (KT + SK - 1) / SK;
+#pragma unroll
+    for (int s0 = 0; s0 < NST - 1; ++s0)
+        if (s0 < KT) stage(s0, s0);
+    wait_tiles(min(KT - 1, 2));  // K-tile 0 has landed
+    barrier();
+    if (g == 1) barrier();  // group 1 starts one slot late
+    for (int kt = 0; kt < KT; ++kt) {
+        if constexpr (SPLIT) {
+            if (kt > 0 && kt % TPC == 0) {  // a chain ends: fold it into the running total, start the next at 0
+#pragma unroll
+                for (int i = 0; i < FN; ++i)
+#pragma unroll
+                    for (int j = 0; j < FM; ++j) {
+                        tot[i][j] = kt == TPC ? acc[i][j] : tot[i][j] + acc[i][j];
+                        acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    }
+            }
+        }
+        // ---- L slot
+        const char* base = smem + (kt & (NST - 1)) * SB;
+        f16x8 a[2][FN], b[2][FM];
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+            const int ch = kk * 4 + fc;
+#pragma unroll
+            for (int i = 0; i < FN; ++i) {
+                const int row = wn * FN * 16 + i * 16 + fr;
+                a[kk][i] = *(const f16x8*)(base + row * 128 + ((ch ^ swz(row)) << 4));
+            }
+#pragma unroll
+            for (int j = 0; j < FM; ++j) {
+                const int row = BN + g * 64 + wm * FM * 16 + j * 16 + fr;
+                b[kk][j] = *(const f16x8*)(base + row * 128 + ((ch ^ swz(row)) << 4));
+            }
+        }
+        if (kt + NST - 1 < KT) stage(kt + NST - 1, (kt + NST - 1) & (NST - 1));
+        if (kt + 1 < KT) wait_tiles(min(KT - 2 - kt, 2));  // K-tile kt + 1 has landed; kt + 2, kt + 3 may fly
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        barrier();
+        // ---- M slot
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+            for (int i = 0; i < FN; ++i)
+#pragma unroll
+                for (int j = 0; j < FM; ++j) acc[i][j] = mfma16(a[kk][i], b[kk][j], acc[i][j]);
+        __builtin_amdgcn_s_setprio(0);
+        barrier();
+    }
+    if (g == 0) barrier();  // same barrier count for both groups
+    if constexpr (SPLIT) {
+        if (KT > TPC) {
+#pragma unroll
+            for (int i = 0; i < FN; ++i)
+#pragma unroll
+                for (int j = 0; j < FM; ++j) acc[i][j] = tot[i][j] + acc[i][j];
+        }
+    }
+    store_frags<EPI>(Y, ldy, bias, M, N, n0 + wn * FN * 16, m0 + g * 64 + wm * FM * 16, fr, fc, acc);
+}
+
 // ------------------------------------------------------------------------------------------------ chains
 // gemm_chains<SK, EPI> (round 5): the SK = k_chains(K) = 2 or 4 K chains of the canonical order computed side by
 // side instead of one after the other.  A workgroup of 4 * SK waves owns one 64 x 64 tile; wave group c (4 waves of
@@ -1365,6 +1511,7 @@ enum GemmCfg {
     CFG_C64,                                          // 64 x 64, the K chains side by side (K > 1024; round 5)
     CFG_T96x128_3, CFG_T96x128_4,                     // 96 weight rows x 128, 4 waves of 48 x 64, 3 / 4 stages
     CFG_PH256, CFG_PH192,                             // 256 / 192 x 256, phase-pipelined wave groups (K <= 1024)
+    CFG_PH96,                                         // 96 x 128, 8 waves of 48 x 32 on a four-deep ring (any K)
     CFG_COUNT
 };
 
@@ -1482,6 +1629,14 @@ static void launch_cfg(int cfg, const f16* x, int64_t ldx, const f16* wt, int64_
                                    ldy, M, N, K);
             }
             break;
+        case CFG_PH96:
+            if (split)
+                hipLaunchKernelGGL((gemm_ph96<EPI, true>), tiles(96, 128), dim3(512), 0, st, x, ldx, wt, ldw, bias, y,
+                                   ldy, M, N, K);
+            else
+                hipLaunchKernelGGL((gemm_ph96<EPI, false>), tiles(96, 128), dim3(512), 0, st, x, ldx, wt, ldw, bias, y,
+                                   ldy, M, N, K);
+            break;
         case CFG_C64: {
             const int sk = k_chains(K);
             if (sk == 4)
@@ -1532,7 +1687,7 @@ static void launch_cfg(int cfg, const f16* x, int64_t ldx, const f16* wt, int64_
 // at M = 16 ... 4096 on GPT-2 shapes (profiles/lmprobe_r02j_*.jsonl): 64 x 64 LDS tiles for the short-K GEMMs
 // from M = 16 up; direct waves for the long-K (split) GEMM up to M = 256, where spreading the chains over
 // waves beats tiling; 128 x 128 tiles for the vocabulary-wide head at large M, and 192 / 256 x 256 phase-pipelined
-// tiles for the wide one-chain GEMMs at B >= 4096.
+// tiles for the wide one-chain GEMMs at B >= 4096, and 96 x 128 tiles, one per CU, for the narrow ones there.
 static int auto_cfg(int M, int N, int K) {
     const bool split = k_chains(K) > 1;
     if (M <= 16) return (N >= 8192 && !split) ? CFG_T64_2 : CFG_DIRECT16;
@@ -1554,6 +1709,11 @@ static int auto_cfg(int M, int N, int K) {
         return w192 < w256 ? CFG_PH192 : CFG_PH256;
     }
     if (!split && M >= 1024 && N >= 4096) return CFG_T128x64_3;
+    // B >= 4096, narrow N, no more 96 x 128 tiles than CUs (GPT-2's attn c_proj and mlp c_proj at B = 4,096: 256
+    // tiles): the 8-wave 96 x 128 kernel, which copies 0.6 of the 64 x 64 tiles' bytes from L2 into LDS.  Chosen
+    // by the kernels' time inside the decode step (mlp c_proj 42.8 -> 33.7 us, attn c_proj 14.5 -> 13.7; the
+    // back-to-back probe on hot operands has attn c_proj 5 % slower, on cold ones 6 % faster; profiles/r09/)
+    if (M >= 4096 && N < 2048 && (long)((M + 127) / 128) * ((N + 95) / 96) <= cu_count()) return CFG_PH96;
     // long K (two or four chains) with few 64 x 64 tiles: the chains side by side (GPT-2-medium's mlp c_proj at
     // B = 1,024: 416 vs 292 TFLOP/s sequential, hipBLASLt 365); with more tiles than two per CU the sequential
     // form keeps more workgroups in flight (GPT-2's at B = 4,096: 540 vs 423; profiles/r05/lmprobe_r05k_*.jsonl)

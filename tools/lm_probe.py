@@ -3,7 +3,10 @@
 For one batch size B: each GEMM of a decode step (c_attn, attn c_proj, c_fc, mlp c_proj, lm head) timed on
 ns_lm_gemm and on torch.addmm/matmul (TFLOP/s), and a layer norm.  HIP events on the launch stream; prints JSON
 lines.  The decode attention is timed by tools/paged_attn_probe.py (paged and dense layouts).
-usage: python tools/lm_probe.py [--batch 4096] [--model gpt2] [--reps 20] [--configs]
+--cold: each GEMM cycles over enough distinct operand sets (activations, weights, output) to exceed the 256 MiB
+Infinity Cache, so every launch finds its operands in HBM as it does inside a decode step, where a layer's weights
+and activations were last touched a whole step ago; without it the launches re-read hot buffers.
+usage: python tools/lm_probe.py [--batch 4096] [--model gpt2] [--reps 20] [--configs] [--cold]
 """
 
 from __future__ import annotations
@@ -23,6 +26,7 @@ def main():
     ap.add_argument("--model", default="gpt2")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--configs", action="store_true", help="time every ns_lm_gemm_config tile configuration")
+    ap.add_argument("--cold", action="store_true", help="cycle over operand sets larger than the Infinity Cache")
     args = ap.parse_args()
     import torch
 
@@ -61,19 +65,30 @@ def main():
         y = torch.empty((B, N), device=dev, dtype=torch.float32 if epi == 3 else torch.float16)
         st = _stream_handle()
         bp = bias.data_ptr() if bias is not None else None
+        # operand sets: one (hot), or as many copies as exceed the cache with one to spare (cold)
+        set_bytes = xa.nbytes + wt.nbytes + y.nbytes
+        nsets = 2 + (320 << 20) // set_bytes if args.cold else 1
+        sets = [(xa, wt, w, y)] + [(xa.clone(), wt.clone(), w.clone(), torch.empty_like(y)) for _ in range(nsets - 1)]
+        turn = [0]
+
+        def next_set():
+            turn[0] = (turn[0] + 1) % nsets
+            return sets[turn[0]]
 
         def native():
-            rc = L.ns_lm_gemm(xa.data_ptr(), K, wt.data_ptr(), K, bp, y.data_ptr(), N, B, N, K, epi, st)
+            xs, ws, _, ys = next_set()
+            rc = L.ns_lm_gemm(xs.data_ptr(), K, ws.data_ptr(), K, bp, ys.data_ptr(), N, B, N, K, epi, st)
             assert rc == 0
 
         def ref():
+            xs, _, wr, _ = next_set()
             if bias is not None:
-                return torch.addmm(bias, xa, w)
-            return xa @ w
+                return torch.addmm(bias, xs, wr)
+            return xs @ wr
 
         ms_n, ms_t = timed(native), timed(ref)
         fl = 2.0 * B * N * K
-        rec = {"gemm": name, "M": B, "N": N, "K": K, "ms_native": ms_n, "ms_torch": ms_t,
+        rec = {"gemm": name, "M": B, "N": N, "K": K, "operand_sets": nsets, "ms_native": ms_n, "ms_torch": ms_t,
                "tflops_native": fl / ms_n / 1e9, "tflops_torch": fl / ms_t / 1e9}
         if args.configs:
             per = {}
@@ -82,7 +97,8 @@ def main():
                     continue  # direct (small-batch) kernels re-read the weights per 64 rows
 
                 def one(cfg=cfg):
-                    rc = L.ns_lm_gemm_config(xa.data_ptr(), K, wt.data_ptr(), K, bp, y.data_ptr(), N, B, N, K, epi,
+                    xs, ws, _, ys = next_set()
+                    rc = L.ns_lm_gemm_config(xs.data_ptr(), K, ws.data_ptr(), K, bp, ys.data_ptr(), N, B, N, K, epi,
                                              cfg, st)
                     assert rc == 0
 
