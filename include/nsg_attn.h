@@ -121,6 +121,30 @@ int ns_decode_attention_paged(const void* d_qkv, int64_t qkv_stride, const uint6
 int ns_seq_attention(const void* d_qkv, int64_t qkv_stride, void* d_out, int64_t out_stride, int B, int T, int H,
                      int D, float scale, void* hip_stream);
 
+/* ns_seq_attention over n_seq sequences of DIFFERENT lengths packed back to back, with the K/V of every sequence
+ * optionally written into that stream's KV pages: the prefill of one context PER message
+ * (src/neuralstego/api.py:707-747, a seed text per stego_encode call).
+ *   d_qkv       fp16 [R, qkv_stride], d_out fp16 [R, out_stride]; sequence s is rows d_seq_start[s] ..
+ *               d_seq_start[s + 1] - 1 (d_seq_start: int32 [n_seq + 1], device, ascending, last = R).
+ *   d_blocks    int32 [nblk][2], device: (sequence, 64-query block) for every block of every sequence, each once,
+ *               longest (highest block index) first; the grid is nblk x H.  The host knows every length and builds
+ *               the list.  An entry that names no block inside the R rows is skipped.
+ * Same arithmetic, block order and MFMA chains as ns_seq_attention: a sequence's output rows are the bits of
+ * ns_seq_attention(B = 1, T = its length) on its own rows, whatever else is packed around it; a workgroup reads
+ * rows of its own sequence only (row clamps stay inside it).
+ * d_page_table != NULL: sequence s's row r (r < its length) is also stored at page
+ * d_page_table[d_seq_slot[s] * table_stride + r / 32] (entries 0 .. max_chunks-1; d_seq_slot int32 [n_seq], values in
+ * [0, n_slots)), at layer_offset + [K|V][H][32][D] as ns_decode_attention_paged reads it: NS_KV_FP16 copies the qkv
+ * values, NS_KV_FP8 converts them as the decode step's append does, so a prefilled row equals an appended one.
+ * Every (sequence, head, row) is written exactly once, by the workgroup of the row's own block; rows of a zero (or
+ * misaligned) table entry, of a chunk >= max_chunks or of a slot outside [0, n_slots) are not stored.  d_page_table
+ * NULL: attention only (the remaining arguments are ignored).  D must be 64. */
+int ns_seq_attention_ragged(const void* d_qkv, int64_t qkv_stride, void* d_out, int64_t out_stride,
+                            const int32_t* d_seq_start, int n_seq, int R, const int32_t* d_blocks, int nblk, int H,
+                            int D, float scale, const uint64_t* d_page_table, int64_t table_stride, int max_chunks,
+                            const int32_t* d_seq_slot, int n_slots, int64_t layer_offset, int kv_format,
+                            void* hip_stream);
+
 /* fp16 [n] -> fp8 e4m3fn [n] with the attention's conversion (n % 4 == 0, 8-byte aligned). */
 int ns_quantize_fp8(const void* d_src, void* d_dst, int64_t n, void* hip_stream);
 

@@ -1094,20 +1094,31 @@ __device__ __forceinline__ _Float16 sq_h(float v) {  // fp32 pinned before the c
     return (_Float16)v;
 }
 
-__global__ __launch_bounds__(256) void seq_attn_kernel(const _Float16* __restrict__ qkv, int64_t qkv_stride,
-                                                       _Float16* __restrict__ out, int64_t out_stride, int T, int H,
-                                                       float scale_log2) {
+// Where the ragged form (ns_seq_attention_ragged) keeps a sequence's K/V: stream row r of the sequence goes to page
+// table[r / 32] (the sequence's table row), at layer_off + [K|V][H][32][D] as ns_decode_attention_paged reads it.
+struct SeqStore {
+    const uint64_t* table;  // the sequence's table row (entries 0..max_chunks-1; 0 = no page: rows not stored)
+    int max_chunks;
+    int64_t layer_off;      // elements from a page's address to this layer's K block
+    int64_t v_off;          // elements from the K block to the V block (H * 32 * D)
+};
+
+// One workgroup: the 64 queries of block qb of ONE sequence of T rows, head columns at `base` (the sequence's first
+// qkv row + h * D), output rows at `obase` (its first output row + h * D).  Every row index is clamped into the
+// sequence (min(row, T - 1)): no row outside [0, T) of the sequence is read.  STORE 0: attention only (the bits
+// of ns_seq_attention); 1 / 2: the workgroup also writes the 64 keys it stages for its own diagonal block
+// (kb == qb, rows < T) to the sequence's pages, fp16 copies / fp8 with the decode append's conversion (pack4_fp8
+// over 4 consecutive dims, as FmtF8::from_qkv) -- every (sequence, head, block) exactly once, from the registers
+// the staging holds anyway.
+template <int STORE>
+__device__ __forceinline__ void seq_attn_block(const _Float16* __restrict__ base, int64_t qkv_stride,
+                                               _Float16* __restrict__ obase, int64_t out_stride, int T, int qb, int h,
+                                               int C, float scale_log2, const SeqStore& ps) {
     __shared__ __attribute__((aligned(16))) _Float16 sK[64 * ATT_D];
     __shared__ __attribute__((aligned(16))) _Float16 sVt[ATT_D * 64];
     __shared__ __attribute__((aligned(16))) _Float16 sP[4][16 * 64];
-    const int nqb = (T + 63) / 64;
-    const int qb = nqb - 1 - (int)(blockIdx.x % nqb);  // the longest query blocks of a pair are dispatched first
-    const int bh = (int)(blockIdx.x / nqb);
-    const int h = bh % H, b = bh / H;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 15, c = lane >> 4;
-    const int C = H * ATT_D;
-    const _Float16* base = qkv + (int64_t)b * T * qkv_stride + h * ATT_D;
     const int tq = qb * 64 + wave * 16 + r;  // this lane's query (padding rows past T are computed, not stored)
     f16x8 qf[2];
 #pragma unroll
@@ -1127,6 +1138,29 @@ __global__ __launch_bounds__(256) void seq_attn_kernel(const _Float16* __restric
             const f16x8 kv = *(const f16x8*)(src + C);
             const f16x8 vv = *(const f16x8*)(src + 2 * C);
             *(f16x8*)(sK + key * 64 + ((ch ^ sq_swz(key)) * 8)) = kv;
+            if constexpr (STORE != 0) {
+                const int row = kb * 64 + key;  // uniform test first: only the diagonal block's workgroup stores
+                if (kb == qb && row < T && (row >> 5) < ps.max_chunks) {
+                    const uint64_t pg = ps.table[row >> 5];
+                    if (pg != 0 && !(pg & 15u)) {
+                        const int64_t e = ps.layer_off + (int64_t)h * 32 * ATT_D + (int64_t)(row & 31) * ATT_D + ch * 8;
+                        if constexpr (STORE == 1) {
+                            _Float16* kd = (_Float16*)pg + e;
+                            *(f16x8*)kd = kv;
+                            *(f16x8*)(kd + ps.v_off) = vv;
+                        } else {
+                            uint8_t* kd = (uint8_t*)pg + e;
+                            uint2 k8, v8;
+                            k8.x = pack4_fp8((float)kv[0], (float)kv[1], (float)kv[2], (float)kv[3]);
+                            k8.y = pack4_fp8((float)kv[4], (float)kv[5], (float)kv[6], (float)kv[7]);
+                            v8.x = pack4_fp8((float)vv[0], (float)vv[1], (float)vv[2], (float)vv[3]);
+                            v8.y = pack4_fp8((float)vv[4], (float)vv[5], (float)vv[6], (float)vv[7]);
+                            *(uint2*)kd = k8;
+                            *(uint2*)(kd + ps.v_off) = v8;
+                        }
+                    }
+                }
+            }
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const int d = ch * 8 + i;
@@ -1184,7 +1218,7 @@ __global__ __launch_bounds__(256) void seq_attn_kernel(const _Float16* __restric
     l += __shfl_xor(l, 32);
     if (tq >= T) return;
     const float inv = 1.0f / l;
-    _Float16* orow = out + (int64_t)(b * T + tq) * out_stride + h * ATT_D;
+    _Float16* orow = obase + (int64_t)tq * out_stride;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) {
         sq_f16x4 v;
@@ -1192,6 +1226,50 @@ __global__ __launch_bounds__(256) void seq_attn_kernel(const _Float16* __restric
         for (int i = 0; i < 4; ++i) v[i] = sq_h(o[dt][i] * inv);
         *(sq_f16x4*)(orow + dt * 16 + 4 * c) = v;
     }
+}
+
+__global__ __launch_bounds__(256) void seq_attn_kernel(const _Float16* __restrict__ qkv, int64_t qkv_stride,
+                                                       _Float16* __restrict__ out, int64_t out_stride, int T, int H,
+                                                       float scale_log2) {
+    const int nqb = (T + 63) / 64;
+    const int qb = nqb - 1 - (int)(blockIdx.x % nqb);  // the longest query blocks of a pair are dispatched first
+    const int bh = (int)(blockIdx.x / nqb);
+    const int h = bh % H, b = bh / H;
+    seq_attn_block<0>(qkv + (int64_t)b * T * qkv_stride + h * ATT_D, qkv_stride,
+                      out + (int64_t)b * T * out_stride + h * ATT_D, out_stride, T, qb, h, H * ATT_D, scale_log2,
+                      SeqStore{});
+}
+
+// Ragged form: n_seq sequences packed back to back (sequence s = rows seq_start[s] .. seq_start[s + 1] - 1 of the
+// R packed rows); workgroup (i, h) serves entry i of the host's block list, (sequence, 64-query block), longest
+// blocks first.  A list entry or an offset pair that does not describe a block inside the R rows retires the
+// workgroup before it reads a row (uniform, ahead of every barrier).  STORE as in seq_attn_block.
+template <int STORE>
+__global__ __launch_bounds__(256) void seq_attn_ragged_kernel(const _Float16* __restrict__ qkv, int64_t qkv_stride,
+                                                              _Float16* __restrict__ out, int64_t out_stride,
+                                                              const int32_t* __restrict__ seq_start, int n_seq, int R,
+                                                              const int32_t* __restrict__ blocks, int H,
+                                                              float scale_log2, const uint64_t* __restrict__ table,
+                                                              int64_t tstride, int max_chunks,
+                                                              const int32_t* __restrict__ seq_slot, int n_slots,
+                                                              int64_t layer_off) {
+    const int i = (int)(blockIdx.x / H), h = (int)(blockIdx.x % H);
+    const int s = blocks[2 * i], qb = blocks[2 * i + 1];
+    if (s < 0 || s >= n_seq || qb < 0) return;
+    const int r0 = seq_start[s], T = seq_start[s + 1] - r0;
+    if (r0 < 0 || T < 1 || T > R - r0 || (int64_t)qb * 64 >= T) return;
+    SeqStore ps{};
+    if constexpr (STORE != 0) {
+        const int slot = seq_slot[s];
+        if (slot >= 0 && slot < n_slots) {  // (a slot outside the table: attention only, nothing stored)
+            ps.table = table + (int64_t)slot * tstride;
+            ps.max_chunks = max_chunks;
+        }
+        ps.layer_off = layer_off;
+        ps.v_off = (int64_t)H * 32 * ATT_D;
+    }
+    seq_attn_block<STORE>(qkv + (int64_t)r0 * qkv_stride + h * ATT_D, qkv_stride,
+                          out + (int64_t)r0 * out_stride + h * ATT_D, out_stride, T, qb, h, H * ATT_D, scale_log2, ps);
 }
 
 }  // namespace nsg
@@ -1395,5 +1473,44 @@ extern "C" int ns_seq_attention(const void* d_qkv, int64_t qkv_stride, void* d_o
     hipLaunchKernelGGL(nsg::seq_attn_kernel, dim3((unsigned)nwg), dim3(256), 0, (hipStream_t)hip_stream,
                        (const _Float16*)d_qkv, qkv_stride, (_Float16*)d_out, out_stride, T, H,
                        scale * 1.4426950408889634f);
+    return hipGetLastError() == hipSuccess ? NS_OK : NS_ERR_HIP;
+}
+
+extern "C" int ns_seq_attention_ragged(const void* d_qkv, int64_t qkv_stride, void* d_out, int64_t out_stride,
+                                       const int32_t* d_seq_start, int n_seq, int R, const int32_t* d_blocks,
+                                       int nblk, int H, int D, float scale, const uint64_t* d_page_table,
+                                       int64_t table_stride, int max_chunks, const int32_t* d_seq_slot, int n_slots,
+                                       int64_t layer_offset, int kv_format, void* hip_stream) {
+    if (!d_qkv || !d_out || !d_seq_start || !d_blocks || n_seq < 1 || R < n_seq || nblk < 1 || H < 1)
+        return NS_ERR_CONFIG;
+    if (D != nsg::ATT_D) return NS_ERR_UNSUPPORTED;
+    if (qkv_stride < 3LL * H * D || out_stride < (int64_t)H * D || (qkv_stride & 7) || (out_stride & 3) ||
+        (((uintptr_t)d_qkv | (uintptr_t)d_out) & 15u) || (((uintptr_t)d_seq_start | (uintptr_t)d_blocks) & 3u))
+        return NS_ERR_CONFIG;
+    if (nblk > (R + 63) / 64 + n_seq) return NS_ERR_CONFIG;  // more entries than the R rows can have blocks
+    if ((int64_t)nblk * H > 0x7FFFFFFF) return NS_ERR_UNSUPPORTED;
+    const dim3 grid((unsigned)((int64_t)nblk * H)), wg(256);
+    const hipStream_t st = (hipStream_t)hip_stream;
+    const _Float16* q = (const _Float16*)d_qkv;
+    _Float16* o = (_Float16*)d_out;
+    const float sl2 = scale * 1.4426950408889634f;
+    if (!d_page_table) {
+        hipLaunchKernelGGL(nsg::seq_attn_ragged_kernel<0>, grid, wg, 0, st, q, qkv_stride, o, out_stride, d_seq_start,
+                           n_seq, R, d_blocks, H, sl2, nullptr, 0, 0, nullptr, 0, 0);
+        return hipGetLastError() == hipSuccess ? NS_OK : NS_ERR_HIP;
+    }
+    if (kv_format != NS_KV_FP16 && kv_format != NS_KV_FP8) return NS_ERR_CONFIG;
+    if (!d_seq_slot || n_slots < 1 || max_chunks < 1 || table_stride < max_chunks || layer_offset < 0 ||
+        ((uintptr_t)d_page_table & 7u) || ((uintptr_t)d_seq_slot & 3u))
+        return NS_ERR_CONFIG;
+    if (layer_offset % (kv_format == NS_KV_FP8 ? 16 : 8)) return NS_ERR_CONFIG;  // 16-byte rows
+    if (kv_format == NS_KV_FP8)
+        hipLaunchKernelGGL(nsg::seq_attn_ragged_kernel<2>, grid, wg, 0, st, q, qkv_stride, o, out_stride, d_seq_start,
+                           n_seq, R, d_blocks, H, sl2, d_page_table, table_stride, max_chunks, d_seq_slot, n_slots,
+                           layer_offset);
+    else
+        hipLaunchKernelGGL(nsg::seq_attn_ragged_kernel<1>, grid, wg, 0, st, q, qkv_stride, o, out_stride, d_seq_start,
+                           n_seq, R, d_blocks, H, sl2, d_page_table, table_stride, max_chunks, d_seq_slot, n_slots,
+                           layer_offset);
     return hipGetLastError() == hipSuccess ? NS_OK : NS_ERR_HIP;
 }

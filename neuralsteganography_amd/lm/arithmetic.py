@@ -265,7 +265,8 @@ class HipArithmeticLM:
         self._decode_states = deque(dict(s) for s in states)
 
     # ---------------------------------------------------------------- batched entry points
-    def encode_batch(self, bit_lists: Sequence[Sequence[int]], context: Sequence[int], *,
+    def encode_batch(self, bit_lists: Sequence[Sequence[int]], context: Optional[Sequence[int]] = None, *,
+                     contexts: Optional[Sequence[Sequence[int]]] = None,
                      quality: Mapping[str, object], check_every: int = 16,
                      stall_steps: int = 4096, return_stats: bool = False, stop_text: Optional[str] = None,
                      graphs: Optional[bool] = None, slots: Optional[int] = None):
@@ -278,6 +279,12 @@ class HipArithmeticLM:
         A message's tokens do not depend on its slot or neighbours (batch-invariant decode step).  Other LMs (the
         PyTorch fp32 forward, synthetic rows) run the lockstep loop below.
 
+        Exactly one of ``context`` (shared by every message) and ``contexts`` (one per message, e.g. one seed text
+        per conversation) is given.  With ``contexts`` a message's context is prefilled into its slot's own KV pages
+        when it is admitted (``BatchedGPT2.prefill_contexts``); its tokens equal
+        ``encode_batch([bits], contexts[m])[0]`` -- the receiver decodes it alone with that context.  Equal
+        ``contexts`` take the shared-context path; non-native LMs run their lockstep loop once per distinct context.
+
         With ``graphs`` (default) the native model's per-token step is captured once as a hipGraph and replayed,
         which removes the per-launch host cost (it dominates at small batch, and at B = 4096 it keeps the GPU busy
         across the host checks).  Non-native models ignore ``graphs``: their lockstep loop runs eagerly, and its token
@@ -288,8 +295,22 @@ class HipArithmeticLM:
         forever.  Here a stream that fixes no payload bit for ``stall_steps`` tokens raises
         :class:`ArithmeticRangeError` instead of hanging."""
         B = len(bit_lists)
+        context, contexts = _one_or_many(context, contexts, B)
         if B == 0:
             return []
+        if contexts is not None and not getattr(self.lm, "native", False):
+            n_enc, n_dec = len(self._encode_states), len(self._decode_states)
+            res = self._by_context(self.encode_batch, bit_lists, contexts, return_stats,
+                                   quality=quality, check_every=check_every, stall_steps=stall_steps,
+                                   return_stats=return_stats, stop_text=stop_text, graphs=graphs, slots=slots)
+            del self._encode_states[n_enc:]  # the groups queued their bit counts group by group: the caller's order
+            while len(self._decode_states) > n_dec:
+                self._decode_states.pop()
+            for b in bit_lists:
+                sc = _bits_count_state(len(b))
+                self._encode_states.append(sc)
+                self._decode_states.append(dict(sc))
+            return res
         params = coder_params_from_quality(quality, self.vocab, self.logits_dtype, self.banned)
         finish = bool(dict(quality or {}).get("finish_sent", False))
         max_bits = max(len(b) for b in bit_lists)
@@ -306,10 +327,11 @@ class HipArithmeticLM:
                 ctx.set_sentence_end(self.sentence_end_table())
             enc = SlotEncoder(self, ctx, bit_lists, context, slots=S, finish=finish, stop_text=stop_text,
                               stats=return_stats, check_every=check_every, stall_steps=stall_steps, hard_cap=hard_cap,
-                              use_graph=bool(graphs), compact=self.slot_compaction)
+                              use_graph=bool(graphs), compact=self.slot_compaction, contexts=contexts)
             toks, st = enc.run()
             self.last_schedule = {"slots": S, "evictions": enc.evictions, "compactions": enc.compactions,
-                                  "max_live": enc.max_live, "kv_pages_peak": enc.kv_peak}
+                                  "max_live": enc.max_live, "kv_pages_peak": enc.kv_peak,
+                                  "prefill_rows": enc.prefill_rows, "prefill_groups": enc.prefill_groups}
             for b in bit_lists:
                 sc = _bits_count_state(len(b))
                 self._encode_states.append(sc)
@@ -373,18 +395,24 @@ class HipArithmeticLM:
             t += 1
         return sess.tokens()
 
-    def decode_batch(self, token_lists: Sequence[Sequence[int]], context: Sequence[int], *,
+    def decode_batch(self, token_lists: Sequence[Sequence[int]], context: Optional[Sequence[int]] = None, *,
+                     contexts: Optional[Sequence[Sequence[int]]] = None,
                      quality: Mapping[str, object], graphs: Optional[bool] = None,
                      slots: Optional[int] = None) -> List[List[int]]:
         """Decode token lists (ragged); returns every emitted bit (callers truncate).  On the native GPU model the
         lists run through ``slots`` slots (:class:`~neuralsteganography_amd.lm.slots.SlotDecoder`, longest first,
         a message's pages mapped when it is admitted); with ``graphs`` the per-token step (coder + GPT-2 decode) is a
-        replayed hipGraph, as in :meth:`encode_batch`.  Non-native models ignore ``graphs`` (eager lockstep loop)."""
+        replayed hipGraph, as in :meth:`encode_batch`.  Non-native models ignore ``graphs`` (eager lockstep loop).
+        ``context`` / ``contexts`` as in :meth:`encode_batch`: one shared context, or one per token list."""
         from ..codec.errors import DecodeDivergenceError
 
         B = len(token_lists)
+        context, contexts = _one_or_many(context, contexts, B)
         if B == 0:
             return []
+        if contexts is not None and not getattr(self.lm, "native", False):
+            return self._by_context(self.decode_batch, token_lists, contexts, False, quality=quality, graphs=graphs,
+                                    slots=slots)
         for tl in token_lists:  # received ids feed the embedding gather: validate on the host first
             if any((int(t) < 0 or int(t) >= self.vocab) for t in tl):
                 raise DecodeDivergenceError(f"received token id outside [0, {self.vocab})")
@@ -396,9 +424,10 @@ class HipArithmeticLM:
 
             S = max(1, min(B, int(slots) if slots else self.max_batch))
             dec = SlotDecoder(self, self._coder(params, S), token_lists, context, slots=S, use_graph=bool(graphs),
-                              compact=self.slot_compaction)
+                              compact=self.slot_compaction, contexts=contexts)
             out = dec.run()
-            self.last_decode_schedule = {"slots": S, "evictions": dec.evictions, "compactions": dec.compactions}
+            self.last_decode_schedule = {"slots": S, "evictions": dec.evictions, "compactions": dec.compactions,
+                                         "prefill_rows": dec.prefill_rows, "prefill_groups": dec.prefill_groups}
             return out
         ctx = self._coder(params, B)
         sess = DecodeSession(ctx, token_lists)
@@ -408,6 +437,23 @@ class HipArithmeticLM:
             if t + 1 < sess.T:
                 logits = self.lm.step(sess.tok[t])
         return sess.bits()
+
+    def _by_context(self, entry, items, contexts, with_stats: bool, **kw):
+        """Non-native LMs: ``entry`` (``encode_batch`` / ``decode_batch``) once per distinct context over that
+        context's messages, results back in the caller's order."""
+        groups: Dict[tuple, List[int]] = {}
+        for i, c in enumerate(contexts):
+            groups.setdefault(tuple(c), []).append(i)
+        out: List[object] = [None] * len(items)
+        stats: List[object] = [None] * len(items)
+        for c, members in groups.items():
+            res = entry([items[i] for i in members], list(c), **kw)
+            res, st = res if with_stats else (res, None)
+            for j, i in enumerate(members):
+                out[i] = res[j]
+                if st is not None:
+                    stats[i] = st[j]
+        return (out, stats) if with_stats else out
 
     def decode_counted(self, token_lists: Sequence[Sequence[int]], context: Sequence[int], *,
                        quality: Mapping[str, object], done=None, check_every: int = 64):
@@ -567,6 +613,21 @@ class HipArithmeticLM:
             if t + 1 < length:
                 logits = self.lm.step(tok.to(torch.long))
         return sess.tokens(), (sess.stats() if stats else None)
+
+
+def _one_or_many(context, contexts, n: int):
+    """``(context, None)`` for a shared context, ``(None, contexts)`` for one context per message; equal
+    ``contexts`` are a shared context.  Exactly one of the two must be given, and ``contexts`` one per message."""
+    if (context is None) == (contexts is None):
+        raise ConfigurationError("give exactly one of context (shared) and contexts (one per message)")
+    if contexts is None:
+        return context, None
+    ctxs = [[int(t) for t in c] for c in contexts]
+    if len(ctxs) != n:
+        raise ConfigurationError(f"{len(ctxs)} contexts for {n} messages")
+    if all(c == ctxs[0] for c in ctxs):
+        return (ctxs[0] if ctxs else []), None
+    return None, ctxs
 
 
 def stop_candidates(tokenizer, vocab: int, stop_text: str):

@@ -125,6 +125,11 @@ class BatchedGPT2:
         self.kv = None
         self.kv_segment_pages = None  # pages per pool segment (None: from the first call's batch)
         self.first_logits = None  # [1, ld] logits of the shared context (a refilled slot's first coder step)
+        # prefill_contexts: packed context rows per group of whole sequences.  The workspace of a packed row is
+        # about 10 C fp16 values (h, a, o: 3 C, qkv: 3 C, c_fc: 4 C; 15 KB at C = 768), so 65,536 rows is about 1 GB
+        # for GPT-2-small -- derived from those sizes, not measured
+        self.prefill_row_budget = 65536
+        self.last_prefill = None  # {"rows", "groups"} of the last prefill_contexts call
         # optional per-stream done flags read by the decode attention (int32 tensor view [B], bit 0 = finished, e.g.
         # the coder state's flags word): finished streams skip their cache reads; their logits are never used again
         self.done_flags = None
@@ -350,11 +355,36 @@ class BatchedGPT2:
         B, T = ids.shape
         C, H = s.n_embd, s.n_head
         D = C // H
-        M = B * T
+        L = _lib.lib()
+        st = _stream_handle()
+        tok = ids.to(device=self.device, dtype=torch.int32).reshape(B * T).contiguous()
+
+        def embed(h, a, lw0, eps):
+            _check(L.ns_lm_embed_seq_ln(tok.data_ptr(), self.wte.data_ptr(), self.wpe.data_ptr(), s.vocab,
+                                        s.n_positions, T, h.data_ptr(), C, lw0["ln1_w"].data_ptr(),
+                                        lw0["ln1_b"].data_ptr(), a.data_ptr(), C, B * T, C, eps, st),
+                   "ns_lm_embed_seq_ln")
+
+        def attention(i, qkv, o):
+            if kv_hook is not None:
+                kv_hook(i, qkv)
+            _check(L.ns_seq_attention(qkv.data_ptr(), qkv.stride(0), o.data_ptr(), o.stride(0), B, T, H, D,
+                                      1.0 / math.sqrt(D), st), "ns_seq_attention")
+
+        return self._rows_native(B * T, embed, attention)
+
+    def _rows_native(self, M: int, embed, attention) -> torch.Tensor:
+        """The layer stack of :meth:`_seq_native` over ``M`` token rows: ``embed(h, a, layer0, eps)`` fills the
+        residual stream and its ln_1, ``attention(layer, qkv, o)`` turns a layer's ``[M, 3C]`` c_attn output into the
+        ``[M, C]`` attention rows (how the rows group into sequences is the caller's: equal lengths, or ragged)."""
+        from .. import _lib
+        from ..coder import _stream_handle
+
+        s = self.shape
+        C = s.n_embd
         L = _lib.lib()
         st = _stream_handle()
         dev, dt = self.device, self.dtype
-        tok = ids.to(device=dev, dtype=torch.int32).reshape(M).contiguous()
         h = torch.empty((M, C), device=dev, dtype=dt)
         a = torch.empty_like(h)
         o = torch.empty_like(h)
@@ -370,23 +400,98 @@ class BatchedGPT2:
             _check(L.ns_lm_layernorm(x.data_ptr(), C, w.data_ptr(), b.data_ptr(), y.data_ptr(), C, M, C, eps, st),
                    "ns_lm_layernorm")
 
-        lw0 = self.layers[0]
-        _check(L.ns_lm_embed_seq_ln(tok.data_ptr(), self.wte.data_ptr(), self.wpe.data_ptr(), s.vocab, s.n_positions,
-                                    T, h.data_ptr(), C, lw0["ln1_w"].data_ptr(), lw0["ln1_b"].data_ptr(),
-                                    a.data_ptr(), C, M, C, eps, st), "ns_lm_embed_seq_ln")
+        embed(h, a, self.layers[0], eps)
         for i, lw in enumerate(self.layers):
             if i > 0:
                 ln(h, lw["ln1_w"], lw["ln1_b"], a)
             gemm(a, lw["qkv_wt"], lw["qkv_b"], qkv, _lib.NS_LM_EPI_STORE, 3 * C, C)
-            if kv_hook is not None:
-                kv_hook(i, qkv)
-            _check(L.ns_seq_attention(qkv.data_ptr(), qkv.stride(0), o.data_ptr(), o.stride(0), B, T, H, D,
-                                      1.0 / math.sqrt(D), st), "ns_seq_attention")
+            attention(i, qkv, o)
             gemm(o, lw["o_wt"], lw["o_b"], h, _lib.NS_LM_EPI_RESIDUAL, C, C)
             ln(h, lw["ln2_w"], lw["ln2_b"], a)
             gemm(a, lw["fc_wt"], lw["fc_b"], f, _lib.NS_LM_EPI_GELU, 4 * C, C)
             gemm(f, lw["pr_wt"], lw["pr_b"], h, _lib.NS_LM_EPI_RESIDUAL, C, 4 * C)
         return h
+
+    # ------------------------------------------------------------------ one context per stream (native path)
+    @torch.no_grad()
+    def prefill_contexts(self, contexts: Sequence[Sequence[int]], slots) -> torch.Tensor:
+        """Run one context PER stream and leave each in its stream's own KV pages: ``contexts[i]`` (trimmed to its
+        last 1,022 ids as :meth:`prefill` trims) becomes positions ``0..T_i-1`` of slot ``slots[i]`` of a call begun
+        with ``begin_slots(B, 0, ...)`` (pages for those positions are mapped here unless the caller already has).
+        The contexts are packed back to back and run as ragged sequences: embedding + ln_1 at each row's own
+        position, the layer GEMMs over the packed rows, ``ns_seq_attention_ragged`` writing every layer's K/V into
+        the pages.  Sets ``lens[slot] = T_i`` (device and host mirror) and returns the ``[n, ld]`` logits after each
+        context's last token.  Row ``i`` equals ``prefill(contexts[i], 1, ...)``'s logits bit for bit, and the decode
+        steps that follow read the same K/V values in the same order as over a shared prefix: a message's tokens do
+        not depend on how its context reached the cache.  Whole sequences are run in groups of at most
+        ``prefill_row_budget`` packed rows (a longer single context runs alone): grouping bounds the workspace,
+        never the bits."""
+        if not self.native:
+            raise RuntimeError("prefill_contexts needs the native HIP path (fp16 on the GPU)")
+        kv = self.kv
+        if kv is None or kv.T0 != 0:
+            raise RuntimeError("prefill_contexts needs a call begun with begin_slots(B, 0, ...)")
+        ctxs = [[int(t) for t in list(c)[-1022:]] for c in contexts]  # code_base/arithmetic.py:90
+        slots = np.asarray(slots, dtype=np.int64).reshape(-1)
+        n = len(ctxs)
+        if n == 0 or slots.size != n:
+            raise ValueError("one slot per context, at least one context")
+        if np.unique(slots).size != n or slots.min() < 0 or slots.max() >= kv.B:
+            raise ValueError(f"slots must be distinct rows of the {kv.B}-slot table")
+        for c in ctxs:
+            if len(c) < 1:
+                raise ValueError("context must contain at least one token")
+            if min(c) < 0 or max(c) >= self.shape.vocab:  # host check: never gather out of the table
+                raise ValueError(f"context token ids must lie in [0, {self.shape.vocab})")
+        lens = np.asarray([len(c) for c in ctxs], dtype=np.int64)
+        if kv.ensure(slots, lens).size:  # (a scheduler has mapped them already, with room for its next steps)
+            from ..exceptions import KVCapacityError
+
+            raise KVCapacityError("no device memory for the contexts' KV pages")
+        kv.set_lens(slots, lens)
+        out = torch.empty((n, self.ld), device=self.device, dtype=self.logits_dtype)
+        groups = prefill_groups(lens, self.prefill_row_budget)
+        for a, b in groups:
+            out[a:b] = self._prefill_group(ctxs[a:b], slots[a:b])
+        self.last_prefill = {"rows": int(lens.sum()), "groups": len(groups)}
+        return out
+
+    def _prefill_group(self, ctxs: List[List[int]], slots: np.ndarray) -> torch.Tensor:
+        from .. import _lib
+        from ..coder import _stream_handle
+
+        s, kv = self.shape, self.kv
+        C, H = s.n_embd, s.n_head
+        D = C // H
+        L = _lib.lib()
+        st = _stream_handle()
+        dev = self.device
+        lens = [len(c) for c in ctxs]
+        seq_start, blocks = ragged_blocks(lens)
+        R, n = int(seq_start[-1]), len(ctxs)
+        tok = torch.from_numpy(np.concatenate([np.asarray(c, dtype=np.int32) for c in ctxs])).to(dev)
+        pos = torch.from_numpy(np.concatenate([np.arange(t, dtype=np.int32) for t in lens])).to(dev)
+        d_start = torch.from_numpy(seq_start).to(dev)
+        d_blocks = torch.from_numpy(blocks).to(dev)
+        d_slot = torch.from_numpy(slots.astype(np.int32)).to(dev)
+        table = kv.table
+
+        def embed(h, a, lw0, eps):  # row positions = the token's index in its own context (% n_positions inside)
+            _check(L.ns_lm_embed_ln_rows(tok.data_ptr(), self.wte.data_ptr(), self.wpe.data_ptr(), s.vocab,
+                                         s.n_positions, pos.data_ptr(), h.data_ptr(), C, lw0["ln1_w"].data_ptr(),
+                                         lw0["ln1_b"].data_ptr(), a.data_ptr(), C, R, C, eps, st),
+                   "ns_lm_embed_ln_rows")
+
+        def attention(i, qkv, o):
+            _check(L.ns_seq_attention_ragged(qkv.data_ptr(), qkv.stride(0), o.data_ptr(), o.stride(0),
+                                             d_start.data_ptr(), n, R, d_blocks.data_ptr(), blocks.shape[0], H, D,
+                                             1.0 / math.sqrt(D), table.data_ptr(), table.stride(0), kv.width,
+                                             d_slot.data_ptr(), kv.B, kv.pool.layer_offset(i), self._kv_format, st),
+                   "ns_seq_attention_ragged")
+
+        hs = self._rows_native(R, embed, attention)
+        last = torch.from_numpy((seq_start[1:] - 1).astype(np.int64)).to(dev)
+        return self._head_native(hs.index_select(0, last))
 
     def _head_native(self, hrows: torch.Tensor) -> torch.Tensor:
         """ln_f + the head GEMM of ``[R, C]`` residual rows on the native kernels: ``[R, ld]`` logits."""
@@ -479,7 +584,8 @@ class BatchedGPT2:
 
     def begin_slots(self, B: int, T0: int, max_new: int = 32) -> None:
         """A new call over ``B`` stream slots, every one at the shared context (cache length ``T0``): a fresh page
-        table (every page of the pool free again), no page assigned yet."""
+        table (every page of the pool free again), no page assigned yet.  ``T0 = 0``: no shared context (``kp`` /
+        ``vp`` dropped) -- every stream's positions are its own (:meth:`prefill_contexts`)."""
         from .kvpages import PAGE_ROWS, PagedKV
 
         pool = self.page_pool(B)
@@ -487,6 +593,9 @@ class BatchedGPT2:
         pool.reset()
         self.kv = PagedKV(pool, B, T0, (max(1, int(max_new)) + PAGE_ROWS - 1) // PAGE_ROWS + 1)
         self.B, self.L, self.T0 = int(B), int(T0), int(T0)
+        if int(T0) == 0:  # no shared prefix: every position is a stream's own (prefill_contexts)
+            self.kp = self.vp = None
+            self.first_logits = None
         self._nb = None
 
     def warm_pool(self, pages: int = None, B: int = 1) -> int:
@@ -604,7 +713,8 @@ class BatchedGPT2:
     def reserve(self, steps: int) -> bool:
         """Lockstep callers: map the pages every slot needs for the next ``steps`` decode steps (False: the device
         has no memory for them)."""
-        return self.kv.ensure(np.arange(self.kv.B), self.L + int(steps)).size == 0
+        return self.kv.ensure(np.arange(self.kv.B), self.kv.lens_host + int(steps)).size == 0  # lens_host == L, or
+        # each stream's own length after prefill_contexts
 
     def advance(self, n: int = 1) -> None:
         """The host side of ``n`` executed decode steps (the device advanced ``lens`` itself)."""
@@ -638,7 +748,7 @@ class BatchedGPT2:
                 ok = self.reserve(1)
             else:
                 live = np.asarray(live, dtype=bool).reshape(B)
-                ok = self.kv.ensure(np.nonzero(live)[0], self.L + 1).size == 0
+                ok = self.kv.ensure(np.nonzero(live)[0], self.kv.lens_host[live] + 1).size == 0
             if not ok:
                 raise KVCapacityError(f"KV cache full at {self.L} positions for B={B}: no device memory for a page")
             out = torch.empty((B, self.ld), device=self.device, dtype=self.logits_dtype)
@@ -661,6 +771,41 @@ class BatchedGPT2:
             h = self._block(i, h, 1, causal=False)
         self.L += 1
         return self._logits(h[:, -1])
+
+
+def ragged_blocks(lengths):
+    """Host side of ``ns_seq_attention_ragged`` for sequences of ``lengths`` rows packed back to back:
+    ``(seq_start, blocks)`` -- ``seq_start`` int32 ``[n + 1]``, the packed row offsets (cumulative sum), and
+    ``blocks`` int32 ``[nblk, 2]``, every (sequence, 64-query block) once, longest first (a block's work grows with
+    its index: it visits key blocks 0..its own), ties in sequence order."""
+    lens = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    if lens.size == 0 or (lens < 1).any():
+        raise ValueError("every sequence needs at least one row")
+    if int(lens.sum()) > np.iinfo(np.int32).max:
+        raise ValueError("too many packed rows")
+    seq_start = np.zeros(lens.size + 1, dtype=np.int32)
+    seq_start[1:] = np.cumsum(lens)
+    nqb = (lens + 63) // 64
+    seq = np.repeat(np.arange(lens.size, dtype=np.int64), nqb)
+    blk = np.arange(seq.size, dtype=np.int64) - np.repeat(np.cumsum(nqb) - nqb, nqb)
+    order = np.lexsort((seq, -blk))  # block index descending, then sequence
+    blocks = np.stack([seq[order], blk[order]], axis=1).astype(np.int32)
+    return seq_start, np.ascontiguousarray(blocks)
+
+
+def prefill_groups(lengths, row_budget: int):
+    """Split sequences of ``lengths`` rows, in order, into consecutive groups ``(first, end)`` of whole sequences
+    with at most ``row_budget`` rows each; a sequence longer than the budget forms a group of its own."""
+    budget = max(1, int(row_budget))
+    groups, first, rows = [], 0, 0
+    for i, t in enumerate(int(x) for x in lengths):
+        if i > first and rows + t > budget:
+            groups.append((first, i))
+            first, rows = i, 0
+        rows += t
+    if len(lengths) > first:
+        groups.append((first, len(lengths)))
+    return groups
 
 
 def _check(rc: int, what: str) -> None:

@@ -227,13 +227,25 @@ class PagedKV:
             self.table[torch.from_numpy(slots).to(self.table.device), :n] = 0
         self.nch[slots] = 0
 
-    def reset(self, slots) -> None:
-        """``release`` + the slots' cache lengths back to the shared context (a new message starts there)."""
+    def reset(self, slots, lens=None) -> None:
+        """``release`` + the slots' cache lengths back to the shared context (a new message starts there), or to
+        ``lens`` (one length per slot, >= ``T0``: a message whose own context of ``lens - T0`` rows is about to be
+        prefilled into its pages; the caller maps them with :meth:`ensure`)."""
         slots = np.asarray(slots, dtype=np.int64).reshape(-1)
         self.release(slots)
-        if slots.size:
-            self.lens[torch.from_numpy(slots).to(self.lens.device)] = self.T0
-            self.lens_host[slots] = self.T0
+        self.set_lens(slots, self.T0 if lens is None else lens)
+
+    def set_lens(self, slots, lens) -> None:
+        """Cache lengths of ``slots`` (scalar or one per slot, >= ``T0``), on the device and in the host mirror."""
+        slots = np.asarray(slots, dtype=np.int64).reshape(-1)
+        if slots.size == 0:
+            return
+        lens = np.broadcast_to(np.asarray(lens, dtype=np.int64), slots.shape)
+        if (lens < self.T0).any():
+            raise ValueError("a slot's cache length cannot be below the shared prefix")
+        dev = self.lens.device
+        self.lens[torch.from_numpy(slots).to(dev)] = torch.from_numpy(lens.astype(np.int32)).to(dev)
+        self.lens_host[slots] = lens
 
     def advance(self, n: int = 1) -> None:
         self.lens_host += int(n)

@@ -16,6 +16,11 @@ mean), so a lockstep batch spends its steps on finished streams.  Here messages 
 * when the queue is empty and at most half the slots are live, the live slots are COMPACTED into a smaller batch
   (page tables move with their rows, no KV is copied): the GEMMs stop computing finished rows.
 
+With ``contexts`` (one per message, library 0.29) there is no shared context: a slot starts at cache length 0, an
+admission maps the pages of each admitted message's own context plus its next steps, prefills those contexts ragged
+into the pages (``BatchedGPT2.prefill_contexts``, at the host check, outside the step graph) and puts each context's
+logits into its slot's row; an evicted message is prefilled again when it comes back.
+
 A stream's logits are bit-identical whatever the batch it runs in (the decode step is batch-invariant, including the
 paged attention), so a message's tokens are the same alone, in lockstep, or refilled into any slot.  Between host
 checks the step (coder + GPT-2 decode) is one captured hipGraph replay; a graph is re-captured when a buffer it
@@ -96,17 +101,50 @@ def _rows_after(event, side, tensor, rows, ncols=None):
     return host
 
 
+def _trimmed(contexts, n: int) -> List[List[int]]:
+    """One context per message, each trimmed to its last 1,022 ids as the shared prefill trims its one."""
+    ctxs = [[int(t) for t in list(c)[-1022:]] for c in contexts]
+    if len(ctxs) != n:
+        raise ValueError(f"{len(ctxs)} contexts for {n} messages")
+    if any(len(c) < 1 for c in ctxs):
+        raise ValueError("context must contain at least one token")
+    return ctxs
+
+
+def _admissible(queue, contexts, check_every: int, nslots: int, room: int) -> List[int]:
+    """Pop the messages to admit now from the queue's front: at most ``nslots``, while the pages of their contexts
+    and first ``check_every + 1`` positions fit in ``room`` pages (what the pool can still hand out beyond one page
+    per live slot).  The admission then maps exactly these pages."""
+    from .kvpages import PAGE_ROWS
+
+    out, used = [], 0
+    while queue and len(out) < nslots:
+        need = (len(contexts[queue[0]]) + check_every + 1 + PAGE_ROWS - 1) // PAGE_ROWS
+        if used + need > room:
+            break
+        used += need
+        out.append(queue.popleft())
+    return out
+
+
 class SlotEncoder:
     """Encode ``bit_lists`` through ``slots`` slots of ``provider.lm`` (a native :class:`BatchedGPT2`)."""
 
     def __init__(self, provider, ctx, bit_lists: Sequence[Sequence[int]], context: Sequence[int], *, slots: int,
                  finish: bool, stop_text: Optional[str], stats: bool, check_every: int, stall_steps: int,
-                 hard_cap: int, use_graph: bool, compact: bool = True):
+                 hard_cap: int, use_graph: bool, compact: bool = True,
+                 contexts: Optional[Sequence[Sequence[int]]] = None):
         self.p, self.lm, self.ctx = provider, provider.lm, ctx
         self.bits = bit_lists
         self.N = len(bit_lists)
         self.S = max(1, min(int(slots), self.N))
         self.context = context
+        # one context per message (``context`` is then None): every admission prefills the admitted messages'
+        # contexts into their slots' own pages (``BatchedGPT2.prefill_contexts``), no shared prefix
+        self.contexts = _trimmed(contexts, self.N) if contexts is not None else None
+        self.ctx_len = np.zeros(self.S, dtype=np.int64)  # context rows of the message in each slot (per-context)
+        self.prefill_rows = 0
+        self.prefill_groups = 0
         self.finish, self.stop_text, self.stats = finish, stop_text, stats
         self.check_every, self.stall_steps, self.hard_cap = int(check_every), int(stall_steps), int(hard_cap)
         self.use_graph, self.allow_compact = use_graph, compact
@@ -126,14 +164,25 @@ class SlotEncoder:
         max_bits = max(len(b) for b in self.bits)
         # initial token-history / page-table width (both grow on demand; a provider may set a small one in tests)
         budget = getattr(self.p, "slot_budget_tokens", None) or 2 * max_bits + 64
-        logits = lm.prefill(self.context, S, budget)  # [S, ld]: every slot starts on the context's logits
-        first = lm.first_logits
+        per_ctx = self.contexts is not None
+        if per_ctx:  # no shared prefix: every slot starts empty and the first check admits from the queue
+            lm.begin_slots(S, 0, budget)
+            logits = torch.zeros((S, lm.ld), device=lm.device, dtype=lm.logits_dtype)
+            first = None
+        else:
+            logits = lm.prefill(self.context, S, budget)  # [S, ld]: every slot starts on the context's logits
+            first = lm.first_logits
         T0 = lm.kv.T0
         stride = max(1, (max_bits + 7) // 8)
         sess = EncodeSession(self.ctx, self.bits[:S], max_tokens=budget, stats=self.stats, payload_stride=stride)
         stop = _StopCheck(self.p, sess, self.stop_text) if self.stop_text is not None else None
-        slot_msg = np.arange(S, dtype=np.int64)  # message per slot, -1 = empty
-        queue = deque(range(S, N))
+        if per_ctx:
+            sess.park_slots(np.arange(S))
+            slot_msg = np.full(S, -1, dtype=np.int64)
+            queue = deque(range(N))
+        else:
+            slot_msg = np.arange(S, dtype=np.int64)  # message per slot, -1 = empty
+            queue = deque(range(S, N))
         tokens: List[Optional[List[int]]] = [None] * N
         stats_out: List[Optional[dict]] = [None] * N
         last_pos = np.zeros(S, dtype=np.int64)
@@ -224,17 +273,31 @@ class SlotEncoder:
                     empty = np.nonzero(~live)[0]
                     if queue and empty.size and not admit_blocked:
                         room = lm.pool.free_pages + lm.pool.growable_pages() - int(live.sum()) - 1
-                        n_adm = int(min(empty.size, len(queue), max(0, room)))
-                        if n_adm:
-                            sl = empty[:n_adm]
-                            ms = [queue.popleft() for _ in range(n_adm)]
-                            self._admit(sess, logits, first, sl, ms, slot_msg, last_pos, last_move, t)
-                            live = slot_msg >= 0
+                        if per_ctx:
+                            ms = _admissible(queue, self.contexts, self.check_every, empty.size, room)
+                            if ms:
+                                back = self._admit_contexts(sess, logits, empty[:len(ms)], ms, slot_msg, last_pos,
+                                                            last_move, t)
+                                queue.extendleft(reversed(back))
+                                admit_blocked = bool(back)
+                                live = slot_msg >= 0
+                        else:
+                            n_adm = int(min(empty.size, len(queue), max(0, room)))
+                            if n_adm:
+                                sl = empty[:n_adm]
+                                ms = [queue.popleft() for _ in range(n_adm)]
+                                self._admit(sess, logits, first, sl, ms, slot_msg, last_pos, last_move, t)
+                                live = slot_msg >= 0
                     nlive = int(live.sum())
                     self.max_live = max(self.max_live, nlive)
                     if nlive == 0:
                         if not queue:
                             break
+                        if per_ctx:
+                            m = queue[0]
+                            raise KVCapacityError(
+                                f"message {m}: no device memory for the KV pages of its {len(self.contexts[m])}-token "
+                                f"context ({lm.pool.total} pages of {lm.pool.page_bytes} B)")
                         raise KVCapacityError("no device memory for even one stream's first KV page")
                     # ---- compaction: the queue is drained and at most half the slots are live
                     compacted = False
@@ -245,6 +308,7 @@ class SlotEncoder:
                         keep = np.nonzero(live)[0]
                         sess, logits, slot_msg, last_pos, last_move = self._compact(
                             sess, logits, keep, slot_msg, last_pos, last_move, stop)
+                        self.ctx_len = self.ctx_len[keep].copy()
                         if stop is not None:
                             stop.sess = sess
                             stop.hit = torch.zeros(sess.B, dtype=torch.bool, device=sess.state.device)
@@ -300,6 +364,36 @@ class SlotEncoder:
         last_pos[slots] = 0
         last_move[slots] = t
 
+    def _admit_contexts(self, sess, logits, slots, msgs, slot_msg, last_pos, last_move, t):
+        """Admit ``msgs`` with their own contexts into ``slots``: pages for each context and the next
+        ``check_every + 1`` positions, one ragged prefill of the contexts into those pages, the first logits into the
+        slots' rows.  Returns the messages that could not be given pages (back to the queue, in order)."""
+        import torch
+
+        lm = self.lm
+        slots = np.asarray(slots, dtype=np.int64)
+        tl = np.asarray([len(self.contexts[m]) for m in msgs], dtype=np.int64)
+        lm.kv.reset(slots, lens=tl)
+        failed = set(lm.kv.ensure(slots, tl + self.check_every + 1).tolist())
+        ok = np.asarray([s not in failed for s in slots.tolist()], dtype=bool)
+        back = [m for m, k in zip(msgs, ok) if not k]
+        if not ok.all():
+            lm.kv.reset(slots[~ok])
+        slots, msgs = slots[ok], [m for m, k in zip(msgs, ok) if k]
+        if not msgs:
+            return back
+        first = lm.prefill_contexts([self.contexts[m] for m in msgs], slots)
+        self.prefill_rows += lm.last_prefill["rows"]
+        self.prefill_groups += lm.last_prefill["groups"]
+        sess.load_slots(slots, [self.bits[m] for m in msgs])
+        idx = torch.as_tensor(slots, device=logits.device)
+        logits.index_copy_(0, idx, first.to(logits.dtype))
+        slot_msg[slots] = msgs
+        self.ctx_len[slots] = tl[ok]
+        last_pos[slots] = 0
+        last_move[slots] = t
+        return back
+
     def _map_pages(self, sess, slot_msg, queue, live, T0):
         """Pages for every live slot's next ``check_every + 1`` positions; on a full device evict the youngest live
         messages (fewest positions fed) back to the queue's front until the others are served."""
@@ -315,7 +409,8 @@ class SlotEncoder:
                 raise KVCapacityError(
                     f"message {int(slot_msg[sl[0]])} needs more KV pages than the device holds "
                     f"({lm.pool.total} pages of {lm.pool.page_bytes} B)")
-            victim = np.asarray([sl[np.argmin(lm.kv.lens_host[sl])]])  # the youngest: fewest positions fed
+            # the youngest: fewest positions fed (its own context's rows, prefilled again later, do not count)
+            victim = np.asarray([sl[np.argmin(lm.kv.lens_host[sl] - self.ctx_len[sl])]])
             queue.appendleft(int(slot_msg[victim[0]]))
             lm.kv.release(victim)
             sess.park_slots(victim)
@@ -341,12 +436,16 @@ class SlotDecoder:
     encoder maps them, with the same eviction), and a slot's end is known on the host from its token count."""
 
     def __init__(self, provider, ctx, token_lists: Sequence[Sequence[int]], context: Sequence[int], *, slots: int,
-                 use_graph: bool, check_every: int = 16, compact: bool = True):
+                 use_graph: bool, check_every: int = 16, compact: bool = True,
+                 contexts: Optional[Sequence[Sequence[int]]] = None):
         self.p, self.lm, self.ctx = provider, provider.lm, ctx
         self.lists = token_lists
         self.N = len(token_lists)
         self.S = max(1, min(int(slots), self.N))
         self.context = context
+        self.contexts = _trimmed(contexts, self.N) if contexts is not None else None  # one per message
+        self.prefill_rows = 0
+        self.prefill_groups = 0
         self.use_graph, self.check_every, self.allow_compact = use_graph, int(check_every), compact
         self.compactions = 0
         self.evictions = 0
@@ -362,8 +461,14 @@ class SlotDecoder:
         lens_all = np.asarray([len(t) for t in self.lists], dtype=np.int64)
         Tcap = max(1, int(lens_all.max(initial=0)))
         order = np.argsort(-lens_all, kind="stable")  # longest first: the tail is short messages
-        logits = lm.prefill(self.context, S, Tcap + 1)
-        first = lm.first_logits
+        per_ctx = self.contexts is not None
+        if per_ctx:  # no shared prefix: a message's context is prefilled into its slot's pages at admission
+            lm.begin_slots(S, 0, Tcap + 1)
+            logits = torch.zeros((S, lm.ld), device=lm.device, dtype=lm.logits_dtype)
+            first = None
+        else:
+            logits = lm.prefill(self.context, S, Tcap + 1)
+            first = lm.first_logits
         T0 = lm.kv.T0
         dev = logits.device
         P = self.ctx.params.precision
@@ -373,6 +478,9 @@ class SlotDecoder:
               "stop": torch.zeros(S, dtype=torch.int32, device=dev),
               "state": _state_tensor(S, dev),
               "out_bits": torch.zeros((S, out_stride), dtype=torch.uint8, device=dev)}
+        if per_ctx:  # context rows of the message in each slot: the token index is lens - ctx (moves with compaction)
+            st["ctx"] = torch.zeros(S, dtype=torch.int32, device=dev)
+        ctx_host = np.full(S, T0, dtype=np.int64)
         self.ctx.check(L.lib().ns_init_state(self.ctx._h, _ptr(st["state"]), S, _stream_handle()), "ns_init_state")
         st["state"].view(torch.int32)[:, 7] = L.NS_ST_DONE
         slot_msg = np.full(S, -1, dtype=np.int64)
@@ -386,7 +494,7 @@ class SlotDecoder:
         admit_blocked = False
 
         def body():
-            tix = lm.kv.lens - T0
+            tix = lm.kv.lens - (st["ctx"] if per_ctx else T0)
             idx = tix.clamp(0, Tcap - 1).long().unsqueeze(1)
             tok = torch.gather(st["tokmat"], 1, idx).squeeze(1).contiguous()
             act = (tix < st["nlen"]).to(torch.uint8)
@@ -418,7 +526,7 @@ class SlotDecoder:
                         else:
                             ev, done = None, np.zeros(slot_msg.shape, dtype=bool)
                     else:
-                        ev, done = None, live & ((lm.kv.lens_host - T0) >= nlen_host)
+                        ev, done = None, live & ((lm.kv.lens_host - ctx_host) >= nlen_host)
                     fin = np.nonzero(done)[0]
                     if fin.size:
                         if ev is not None:
@@ -446,24 +554,38 @@ class SlotDecoder:
                     empty = np.nonzero(~live)[0]
                     if queue and empty.size and not admit_blocked:
                         room = lm.pool.free_pages + lm.pool.growable_pages() - int(live.sum()) - 1
-                        n_adm = int(min(empty.size, len(queue), max(0, room)))
-                        if n_adm:
-                            adm_s = empty[:n_adm]
-                            adm_m = [queue.popleft() for _ in range(n_adm)]
-                            lm.kv.reset(adm_s)
-                            self._admit(st, logits, first, init_row, adm_s, adm_m, slot_msg, nlen_host, T0, Tcap)
-                            live = slot_msg >= 0
+                        if per_ctx:
+                            adm_m = _admissible(queue, self.contexts, self.check_every, empty.size, room)
+                            if adm_m:
+                                back = self._admit_contexts(st, logits, init_row, empty[:len(adm_m)], adm_m, slot_msg,
+                                                            nlen_host, ctx_host, Tcap)
+                                queue.extendleft(reversed(back))
+                                admit_blocked = bool(back)
+                                live = slot_msg >= 0
+                            if not live.any():
+                                m = queue[0]
+                                raise KVCapacityError(
+                                    f"message {m}: no device memory for the KV pages of its "
+                                    f"{len(self.contexts[m])}-token context")
+                        else:
+                            n_adm = int(min(empty.size, len(queue), max(0, room)))
+                            if n_adm:
+                                adm_s = empty[:n_adm]
+                                adm_m = [queue.popleft() for _ in range(n_adm)]
+                                lm.kv.reset(adm_s)
+                                self._admit(st, logits, first, init_row, adm_s, adm_m, slot_msg, nlen_host, T0, Tcap)
+                                live = slot_msg >= 0
                     # pages for the next check_every + 1 positions (never past a message's last fed token); on a full
                     # device the youngest messages go back to the queue's front (re-decoded later: the same bits)
                     while live.any():
                         sl = np.nonzero(live)[0]
-                        upto = np.minimum(lm.kv.lens_host[sl] + self.check_every + 1, T0 + nlen_host[sl])
+                        upto = np.minimum(lm.kv.lens_host[sl] + self.check_every + 1, ctx_host[sl] + nlen_host[sl])
                         if lm.kv.ensure(sl, upto).size == 0:
                             break
                         if sl.size == 1:
                             raise KVCapacityError(f"message {int(slot_msg[sl[0]])} ({int(nlen_host[sl[0]])} tokens) "
                                                   "needs more KV pages than the device holds")
-                        v = sl[np.argmin(lm.kv.lens_host[sl])]
+                        v = sl[np.argmin(lm.kv.lens_host[sl] - ctx_host[sl])]  # the youngest: fewest tokens fed
                         queue.appendleft(int(slot_msg[v]))
                         lm.kv.release([v])
                         vi = torch.as_tensor([int(v)], device=dev)
@@ -486,13 +608,15 @@ class SlotDecoder:
                             st[k] = st[k].index_select(0, ki).contiguous()
                         logits = logits.index_select(0, ki).contiguous()
                         slot_msg, nlen_host = slot_msg[keep].copy(), nlen_host[keep].copy()
+                        ctx_host = ctx_host[keep].copy()
                         self.compactions += 1
                     lm.stop_len = st["stop"] if getattr(self.p, "skip_done", True) else None
                     if pipelined:
                         ev_now = torch.cuda.Event()
                         ev_now.record()
-                        pending = (ev_now, slot_msg.copy(), lm.kv.lens_host - T0)
-                key = _layout_key(logits, st["state"], st["tokmat"], lm.kv.table, lm.kv.lens) + (lm.kv.version,)
+                        pending = (ev_now, slot_msg.copy(), lm.kv.lens_host - ctx_host)
+                key = _layout_key(logits, st["state"], st["tokmat"], lm.kv.table, lm.kv.lens, st.get("ctx")) + \
+                    (lm.kv.version,)
                 if self.use_graph:
                     if graph is None or key != gkey:
                         graph = None
@@ -512,7 +636,37 @@ class SlotDecoder:
             del graph
         return out
 
+    def _admit_contexts(self, st, logits, init_row, slots, msgs, slot_msg, nlen_host, ctx_host, Tcap):
+        """Admit ``msgs`` with their own contexts into ``slots``: pages for each context and the message's first
+        positions, one ragged prefill into those pages, then the slot state of :meth:`_admit` with a per-slot context
+        length.  Returns the messages that could not be given pages."""
+        import torch
+
+        lm = self.lm
+        slots = np.asarray(slots, dtype=np.int64)
+        tl = np.asarray([len(self.contexts[m]) for m in msgs], dtype=np.int64)
+        nl = np.asarray([len(self.lists[m]) for m in msgs], dtype=np.int64)
+        lm.kv.reset(slots, lens=tl)
+        failed = set(lm.kv.ensure(slots, tl + np.minimum(self.check_every + 1, nl)).tolist())
+        ok = np.asarray([s not in failed for s in slots.tolist()], dtype=bool)
+        back = [m for m, k in zip(msgs, ok) if not k]
+        if not ok.all():
+            lm.kv.reset(slots[~ok])
+        slots, msgs, tl = slots[ok], [m for m, k in zip(msgs, ok) if k], tl[ok]
+        if not msgs:
+            return back
+        first = lm.prefill_contexts([self.contexts[m] for m in msgs], slots)
+        self.prefill_rows += lm.last_prefill["rows"]
+        self.prefill_groups += lm.last_prefill["groups"]
+        idx = torch.as_tensor(slots, device=logits.device)
+        st["ctx"][idx] = torch.from_numpy(tl.astype(np.int32)).to(logits.device)
+        ctx_host[slots] = tl
+        self._admit(st, logits, first, init_row, slots, msgs, slot_msg, nlen_host, tl, Tcap)
+        return back
+
     def _admit(self, st, logits, first, init_row, slots, msgs, slot_msg, nlen_host, T0, Tcap):
+        """``T0``: the context length of the admitted messages (the shared one, or one per slot); ``first``: the
+        context's ``[1, ld]`` logits, or one row per slot."""
         import torch
 
         dev = logits.device
@@ -528,7 +682,8 @@ class SlotDecoder:
         st["tokmat"][idx] = torch.from_numpy(mat).to(dev)
         nlt = torch.from_numpy(nl.astype(np.int32)).to(dev)
         st["nlen"][idx] = nlt
-        st["stop"][idx] = nlt + (T0 - 1)
+        t0 = T0 if np.isscalar(T0) else torch.from_numpy(np.asarray(T0).astype(np.int32)).to(dev)
+        st["stop"][idx] = nlt + (t0 - 1)
         st["state"][idx] = init_row.expand(n, 4)
         st["out_bits"][idx] = 0
         logits.index_copy_(0, idx, first.expand(n, -1).to(logits.dtype))

@@ -113,10 +113,57 @@ def _decode_streams(lm, spans: List[List[int]], context: List[int], quality: Dic
     return [lm.decode_arithmetic(list(span), context, quality=quality) for span in spans]
 
 
+def _encode_streams_each(lm, bit_lists: List[List[int]], contexts: List[List[int]],
+                         quality: Dict[str, Any]) -> List[List[int]]:
+    """``_encode_streams`` with one context per stream (``seed_texts``).  A provider whose ``encode_batch`` takes
+    one shared context only (the rank coder) is driven per packet, in order, as a provider without one is."""
+    if _takes_contexts(getattr(lm, "encode_batch", None)):
+        return lm.encode_batch(bit_lists, contexts=contexts, quality=quality)
+    return [lm.encode_arithmetic(bits, ctx, quality=quality) for bits, ctx in zip(bit_lists, contexts)]
+
+
+def _decode_streams_each(lm, spans: List[List[int]], contexts: List[List[int]],
+                         quality: Dict[str, Any]) -> List[List[int]]:
+    """``_decode_streams`` with one context per span (``seed_texts``)."""
+    if _takes_contexts(getattr(lm, "decode_batch", None)):
+        if getattr(lm, "decodes_without_state", False):
+            queue = getattr(lm, "_decode_states", None)
+            if queue:
+                for _ in range(min(len(spans), len(queue))):
+                    queue.popleft()
+        return lm.decode_batch(spans, contexts=contexts, quality=quality)
+    return [lm.decode_arithmetic(list(span), ctx, quality=quality) for span, ctx in zip(spans, contexts)]
+
+
+def _takes_contexts(entry) -> bool:
+    import inspect
+
+    if entry is None:
+        return False
+    try:
+        return "contexts" in inspect.signature(entry).parameters
+    except (TypeError, ValueError):
+        return False
+
+
+def _seed_contexts(lm, seed_texts: Sequence[str], n: int) -> List[List[int]]:
+    seeds = list(seed_texts)
+    if len(seeds) != n:
+        raise ConfigurationError(f"{len(seeds)} seed texts for {n} messages")
+    cache: Dict[str, List[int]] = {}
+    for text in seeds:
+        if text not in cache:
+            cache[text] = list(lm.encode_seed(text))
+    return [cache[text] for text in seeds]
+
+
 def stego_encode_batch(messages: Sequence[bytes], *, chunk_bytes: int = 256, use_crc: bool = True,
                        ecc: Optional[str] = "rs", nsym: int = 10, quality: Optional[Dict[str, float]] = None,
-                       seed_text: str = "", lm) -> List[EncodeResult]:
-    """Every message -> its :class:`EncodeResult`; all packets of all messages are encoded as one batch."""
+                       seed_text: str = "", seed_texts: Optional[Sequence[str]] = None, lm) -> List[EncodeResult]:
+    """Every message -> its :class:`EncodeResult`; all packets of all messages are encoded as one batch.
+    ``seed_texts`` (one per message, as each ``stego_encode`` call of the reference has its own ``seed_text``):
+    every packet of message ``i`` is encoded with ``encode_seed(seed_texts[i])``; ``seed_text`` is then unused."""
+    per_msg = _seed_contexts(lm, seed_texts, len(messages)) if seed_texts is not None else None
     mode = normalise_ecc(ecc)
     cfg = {"chunk_bytes": int(chunk_bytes), "crc": bool(use_crc), "ecc": mode, "nsym": int(nsym if mode == "rs" else 0)}
     q = _quality_args(quality)
@@ -130,8 +177,11 @@ def stego_encode_batch(messages: Sequence[bytes], *, chunk_bytes: int = 256, use
         for pkt in build_packets(chunks, msg_id=msg_id, cfg=cfg):
             bit_lists.append(bytes_to_bits_lsb(pkt))
             owner.append(mi)
-    context = list(lm.encode_seed(seed_text))
-    spans = _encode_streams(lm, bit_lists, context, q) if bit_lists else []
+    if per_msg is not None:
+        spans = _encode_streams_each(lm, bit_lists, [per_msg[mi] for mi in owner], q) if bit_lists else []
+    else:
+        context = list(lm.encode_seed(seed_text))
+        spans = _encode_streams(lm, bit_lists, context, q) if bit_lists else []
     per: List[List[List[int]]] = [[] for _ in messages]
     for mi, span in zip(owner, spans):
         per[mi].append([int(t) for t in span])
@@ -174,11 +224,13 @@ def _assemble(packets: List[Packet]) -> bytes:
 
 
 def stego_decode_batch(span_sets: Sequence[Iterable[List[int]]], *, use_crc: bool = True, ecc: Optional[str] = "rs",
-                       nsym: int = 10, quality: Optional[Dict[str, float]] = None, seed_text: str = "", lm,
-                       return_errors: bool = False) -> List[Any]:
+                       nsym: int = 10, quality: Optional[Dict[str, float]] = None, seed_text: str = "",
+                       seed_texts: Optional[Sequence[str]] = None, lm, return_errors: bool = False) -> List[Any]:
     """Every message's spans -> its bytes, all spans decoded as one batch.  Errors (missing chunks, CRC, RS,
     cfg mismatch) raise for the first failing message, or are returned in its slot with
-    ``return_errors=True``."""
+    ``return_errors=True``.  ``seed_texts``: one seed text per message, as in :func:`stego_encode_batch`."""
+    span_sets = list(span_sets)
+    per_msg = _seed_contexts(lm, seed_texts, len(span_sets)) if seed_texts is not None else None
     mode = normalise_ecc(ecc)
     expected = {"crc": bool(use_crc), "ecc": mode, "nsym": int(nsym if mode == "rs" else 0)}
     q = _quality_args(quality)
@@ -188,8 +240,11 @@ def stego_decode_batch(span_sets: Sequence[Iterable[List[int]]], *, use_crc: boo
         for span in spans:
             flat.append([int(t) for t in span])
             owner.append(mi)
-    context = list(lm.encode_seed(seed_text))
-    bits = _decode_streams(lm, flat, context, q) if flat else []
+    if per_msg is not None:
+        bits = _decode_streams_each(lm, flat, [per_msg[mi] for mi in owner], q) if flat else []
+    else:
+        context = list(lm.encode_seed(seed_text))
+        bits = _decode_streams(lm, flat, context, q) if flat else []
     packets: List[List[Packet]] = [[] for _ in span_sets]
     errors: List[Optional[Exception]] = [None] * len(span_sets)
     for mi, b in zip(owner, bits):
