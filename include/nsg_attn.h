@@ -145,6 +145,18 @@ int ns_seq_attention_ragged(const void* d_qkv, int64_t qkv_stride, void* d_out, 
                             const int32_t* d_seq_slot, int n_slots, int64_t layer_offset, int kv_format,
                             void* hip_stream);
 
+/* The head rows of one KV page into another, for many (source, destination) pairs in one launch: a context's KV
+ * pages shared among the messages that carry it -- the context's last, partly filled page is copied into the first
+ * own page of every holder, which that holder then appends into (a shared page is never an append target).
+ * For i < n and every layer l < n_layer: copy rows 0 .. d_rows[i]-1 of K and of V, every head, from the page at
+ * d_src[i] to the page at d_dst[i]  (page = address of its layer-0 block; a layer's block is [K|V][H][32][D] in
+ * the kv_format's element type, layer l at + l*layer_stride elements, as ns_decode_attention_paged reads it).
+ * Bytes are copied as they are (fp16 or fp8).  Rows >= d_rows[i] of the destination, and every other byte, are
+ * not written.  An entry with a zero or misaligned address, d_rows[i] outside [0, 32], or src == dst is skipped.
+ * The caller keeps destinations distinct.  n == 0 returns NS_OK without a launch.  D must be 64. */
+int ns_kv_copy_rows(const uint64_t* d_src, const uint64_t* d_dst, const int32_t* d_rows, int n, int n_layer,
+                    int64_t layer_stride, int H, int D, int kv_format, void* hip_stream);
+
 /* fp16 [n] -> fp8 e4m3fn [n] with the attention's conversion (n % 4 == 0, 8-byte aligned). */
 int ns_quantize_fp8(const void* d_src, void* d_dst, int64_t n, void* hip_stream);
 

@@ -1514,3 +1514,47 @@ extern "C" int ns_seq_attention_ragged(const void* d_qkv, int64_t qkv_stride, vo
                            layer_offset);
     return hipGetLastError() == hipSuccess ? NS_OK : NS_ERR_HIP;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// ns_kv_copy_rows: the head rows of one KV page into another, every layer (a context's KV pages shared among the
+// messages that carry it, lm/kvpages.py: the context's last, partly filled page is copied into each holder's own
+// first page, which the holder then appends into).  One workgroup per (pair, layer): the layer's block is 2H pieces
+// ([K|V][H]) of 32 rows; the first `rows` rows of a piece are rows * row_vecs contiguous 16-byte vectors (a row is
+// 128 B in fp16, 64 B in fp8), so consecutive lanes move consecutive vectors.  Bytes are moved as they are.
+namespace nsg {
+__global__ __launch_bounds__(256) void kv_copy_rows_kernel(const uint64_t* __restrict__ src,
+                                                           const uint64_t* __restrict__ dst,
+                                                           const int32_t* __restrict__ rows, int n, int n_layer,
+                                                           int64_t layer_bytes, int pieces, int row_vecs) {
+    const int pair = (int)(blockIdx.x / (unsigned)n_layer), layer = (int)(blockIdx.x % (unsigned)n_layer);
+    if (pair >= n) return;
+    const uint64_t s = src[pair], d = dst[pair];
+    const int r = rows[pair];
+    if (!s || !d || ((s | d) & 15u) || s == d || r <= 0 || r > 32) return;
+    const uint4* sp = (const uint4*)(s + (uint64_t)layer * (uint64_t)layer_bytes);
+    uint4* dp = (uint4*)(d + (uint64_t)layer * (uint64_t)layer_bytes);
+    const int nv = r * row_vecs, piece_vecs = 32 * row_vecs;  // nv <= 256
+    for (int i = (int)threadIdx.x; i < pieces * nv; i += 256) {
+        const int p = i / nv, v = i - p * nv;
+        dp[p * piece_vecs + v] = sp[p * piece_vecs + v];
+    }
+}
+}  // namespace nsg
+
+extern "C" int ns_kv_copy_rows(const uint64_t* d_src, const uint64_t* d_dst, const int32_t* d_rows, int n,
+                               int n_layer, int64_t layer_stride, int H, int D, int kv_format, void* hip_stream) {
+    if (n < 0 || n_layer < 1 || H < 1 || H > 4096 || D < 1) return NS_ERR_CONFIG;
+    if (D != nsg::ATT_D) return NS_ERR_UNSUPPORTED;
+    if (kv_format != NS_KV_FP16 && kv_format != NS_KV_FP8) return NS_ERR_CONFIG;
+    const int esize = kv_format == NS_KV_FP8 ? 1 : 2;
+    if (layer_stride < 0 || layer_stride % (16 / esize)) return NS_ERR_CONFIG;  // 16-byte vectors
+    if (n_layer > 1 && layer_stride < 2LL * H * 32 * D) return NS_ERR_CONFIG;  // layers' blocks would overlap
+    if (n == 0) return NS_OK;
+    if (!d_src || !d_dst || !d_rows || (((uintptr_t)d_src | (uintptr_t)d_dst) & 7u) || ((uintptr_t)d_rows & 3u))
+        return NS_ERR_CONFIG;
+    if ((int64_t)n * n_layer > 0x7FFFFFFF) return NS_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(nsg::kv_copy_rows_kernel, dim3((unsigned)((int64_t)n * n_layer)), dim3(256), 0,
+                       (hipStream_t)hip_stream, d_src, d_dst, d_rows, n, n_layer, layer_stride * esize, 2 * H,
+                       D * esize / 16);
+    return hipGetLastError() == hipSuccess ? NS_OK : NS_ERR_HIP;
+}

@@ -126,6 +126,7 @@ class HipArithmeticLM:
     skip_done = True  # finished streams skip their attention (encode: done flag, decode: stop position; A/B, tests)
     slot_compaction = True  # native slot loops: compact the live slots once the queue is drained (off: tests that
                             # read per-step logits by row)
+    share_contexts = True  # ``contexts=``: messages with equal contexts share the context's KV pages (off: A/B, tests)
 
     def __init__(self, model, tokenizer=None, *, device: Optional[str] = None, logits_dtype: str = "f32",
                  compute_dtype=None, banned: Optional[Sequence[int]] = None, max_batch: int = 4096,
@@ -282,8 +283,10 @@ class HipArithmeticLM:
         Exactly one of ``context`` (shared by every message) and ``contexts`` (one per message, e.g. one seed text
         per conversation) is given.  With ``contexts`` a message's context is prefilled into its slot's own KV pages
         when it is admitted (``BatchedGPT2.prefill_contexts``); its tokens equal
-        ``encode_batch([bits], contexts[m])[0]`` -- the receiver decodes it alone with that context.  Equal
-        ``contexts`` take the shared-context path; non-native LMs run their lockstep loop once per distinct context.
+        ``encode_batch([bits], contexts[m])[0]`` -- the receiver decodes it alone with that context.  Messages whose
+        contexts are equal share the context's KV pages and one prefill (``share_contexts``, ``lm/kvpages.py``).
+        All-equal ``contexts`` take the shared-context path; non-native LMs run their lockstep loop once per distinct
+        context.
 
         With ``graphs`` (default) the native model's per-token step is captured once as a hipGraph and replayed,
         which removes the per-launch host cost (it dominates at small batch, and at B = 4096 it keeps the GPU busy
@@ -327,11 +330,13 @@ class HipArithmeticLM:
                 ctx.set_sentence_end(self.sentence_end_table())
             enc = SlotEncoder(self, ctx, bit_lists, context, slots=S, finish=finish, stop_text=stop_text,
                               stats=return_stats, check_every=check_every, stall_steps=stall_steps, hard_cap=hard_cap,
-                              use_graph=bool(graphs), compact=self.slot_compaction, contexts=contexts)
+                              use_graph=bool(graphs), compact=self.slot_compaction, contexts=contexts,
+                              share=self.share_contexts)
             toks, st = enc.run()
             self.last_schedule = {"slots": S, "evictions": enc.evictions, "compactions": enc.compactions,
                                   "max_live": enc.max_live, "kv_pages_peak": enc.kv_peak,
-                                  "prefill_rows": enc.prefill_rows, "prefill_groups": enc.prefill_groups}
+                                  "prefill_rows": enc.prefill_rows, "prefill_groups": enc.prefill_groups,
+                                  "prefill_shared": enc.prefill_shared}
             for b in bit_lists:
                 sc = _bits_count_state(len(b))
                 self._encode_states.append(sc)
@@ -424,10 +429,11 @@ class HipArithmeticLM:
 
             S = max(1, min(B, int(slots) if slots else self.max_batch))
             dec = SlotDecoder(self, self._coder(params, S), token_lists, context, slots=S, use_graph=bool(graphs),
-                              compact=self.slot_compaction, contexts=contexts)
+                              compact=self.slot_compaction, contexts=contexts, share=self.share_contexts)
             out = dec.run()
             self.last_decode_schedule = {"slots": S, "evictions": dec.evictions, "compactions": dec.compactions,
-                                         "prefill_rows": dec.prefill_rows, "prefill_groups": dec.prefill_groups}
+                                         "prefill_rows": dec.prefill_rows, "prefill_groups": dec.prefill_groups,
+                                         "prefill_shared": dec.prefill_shared}
             return out
         ctx = self._coder(params, B)
         sess = DecodeSession(ctx, token_lists)

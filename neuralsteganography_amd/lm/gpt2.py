@@ -129,7 +129,8 @@ class BatchedGPT2:
         # about 10 C fp16 values (h, a, o: 3 C, qkv: 3 C, c_fc: 4 C; 15 KB at C = 768), so 65,536 rows is about 1 GB
         # for GPT-2-small -- derived from those sizes, not measured
         self.prefill_row_budget = 65536
-        self.last_prefill = None  # {"rows", "groups"} of the last prefill_contexts call
+        self.last_prefill = None  # {"rows", "groups", "shared"} of the last prefill_contexts call
+        self.share_contexts = True  # equal contexts of a call share their KV pages (off: A/B runs and tests)
         # optional per-stream done flags read by the decode attention (int32 tensor view [B], bit 0 = finished, e.g.
         # the coder state's flags word): finished streams skip their cache reads; their logits are never used again
         self.done_flags = None
@@ -414,7 +415,7 @@ class BatchedGPT2:
 
     # ------------------------------------------------------------------ one context per stream (native path)
     @torch.no_grad()
-    def prefill_contexts(self, contexts: Sequence[Sequence[int]], slots) -> torch.Tensor:
+    def prefill_contexts(self, contexts: Sequence[Sequence[int]], slots, shared=None) -> torch.Tensor:
         """Run one context PER stream and leave each in its stream's own KV pages: ``contexts[i]`` (trimmed to its
         last 1,022 ids as :meth:`prefill` trims) becomes positions ``0..T_i-1`` of slot ``slots[i]`` of a call begun
         with ``begin_slots(B, 0, ...)`` (pages for those positions are mapped here unless the caller already has).
@@ -425,7 +426,16 @@ class BatchedGPT2:
         steps that follow read the same K/V values in the same order as over a shared prefix: a message's tokens do
         not depend on how its context reached the cache.  Whole sequences are run in groups of at most
         ``prefill_row_budget`` packed rows (a longer single context runs alone): grouping bounds the workspace,
-        never the bits."""
+        never the bits.
+
+        Equal contexts share pages (``share_contexts``; ``shared``: one flag per context, from a scheduler that knows
+        the whole call's multiplicities -- default: a context shares when a live entry of ``kv.entries`` holds it or
+        another context of this call equals it).  A sharing context is run once, into its entry's own pages through a
+        small table of those pages, while any slot holds the entry; every holder's table row starts with the entry's
+        full pages, the context's last partial page is copied into the holder's first own page (``ns_kv_copy_rows``:
+        the holder appends into it) and its logits row is the entry's.  The stored bytes are the ones a private
+        prefill stores and the decode step reads by address, so the bits do not change.  ``last_prefill`` has the
+        ``rows`` actually run, the ``groups`` they ran in and ``shared``, the slots served from an entry."""
         if not self.native:
             raise RuntimeError("prefill_contexts needs the native HIP path (fp16 on the GPU)")
         kv = self.kv
@@ -443,20 +453,91 @@ class BatchedGPT2:
                 raise ValueError("context must contain at least one token")
             if min(c) < 0 or max(c) >= self.shape.vocab:  # host check: never gather out of the table
                 raise ValueError(f"context token ids must lie in [0, {self.shape.vocab})")
-        lens = np.asarray([len(c) for c in ctxs], dtype=np.int64)
-        if kv.ensure(slots, lens).size:  # (a scheduler has mapped them already, with room for its next steps)
-            from ..exceptions import KVCapacityError
+        from ..exceptions import KVCapacityError
 
+        lens = np.asarray([len(c) for c in ctxs], dtype=np.int64)
+        if shared is None:  # a context shares when a live entry holds it or another context of this call equals it
+            from .kvpages import sharing_keys
+
+            # only slots that can take a hold (no page mapped yet) or have one are compared: a context whose twin
+            # keeps private pages stays a singleton, it does not open an entry for itself alone
+            el = [i for i, s in enumerate(slots.tolist()) if kv.nch[s] == 0 or kv.slot_entry[s] is not None]
+            keys = [None] * n
+            if self.share_contexts and el:
+                for i, k in zip(el, sharing_keys([ctxs[i] for i in el], kv.entries)):
+                    keys[i] = k
+            sh = np.asarray([k is not None for k in keys], dtype=bool)
+        else:
+            sh = np.asarray(shared, dtype=bool).reshape(-1)
+            if sh.size != n:
+                raise ValueError("one shared flag per context")
+            keys = [tuple(c) if f else None for c, f in zip(ctxs, sh)]
+        # holders: their table rows start with the entry's full pages (a scheduler may have mapped them already)
+        todo = [i for i in np.nonzero(sh)[0].tolist() if kv.slot_entry[slots[i]] is None]
+        if todo and kv.hold(slots[todo], [keys[i] for i in todo], lens[todo]).size:
+            kv.release(slots[todo])
+            raise KVCapacityError("no device memory for a shared context's KV pages")
+        for i in np.nonzero(sh)[0].tolist():
+            if kv.slot_entry[slots[i]].key != keys[i]:
+                raise RuntimeError("prefill_contexts: the slot holds another context")
+        if kv.ensure(slots, lens).size:  # (a scheduler has mapped them already, with room for its next steps)
+            kv.release(slots[todo])  # the holds taken above: no entry stays behind unprefilled
             raise KVCapacityError("no device memory for the contexts' KV pages")
         kv.set_lens(slots, lens)
         out = torch.empty((n, self.ld), device=self.device, dtype=self.logits_dtype)
-        groups = prefill_groups(lens, self.prefill_row_budget)
-        for a, b in groups:
-            out[a:b] = self._prefill_group(ctxs[a:b], slots[a:b])
-        self.last_prefill = {"rows": int(lens.sum()), "groups": len(groups)}
+        rows = ngroups = 0
+        # new entries: each prefilled once, through a table of its own pages
+        new = [e for e in {id(kv.slot_entry[slots[i]]): kv.slot_entry[slots[i]] for i in np.nonzero(sh)[0]}.values()
+               if e.logits is None]
+        if new:
+            etab = np.zeros((len(new), max(e.pages.size for e in new)), dtype=np.int64)
+            for j, e in enumerate(new):
+                etab[j, : e.pages.size] = e.pages
+            d_etab = torch.from_numpy(etab).to(self.device)
+            elens = [e.T for e in new]
+            for a, b in prefill_groups(elens, self.prefill_row_budget):
+                lg = self._prefill_group([list(e.key) for e in new[a:b]], np.arange(a, b), d_etab)
+                for j, e in enumerate(new[a:b]):
+                    e.logits = lg[j:j + 1].clone()
+                ngroups += 1
+            rows += int(sum(elens))
+        # singletons: straight into their slots' own pages
+        single = np.nonzero(~sh)[0]
+        if single.size:
+            for a, b in prefill_groups(lens[single], self.prefill_row_budget):
+                ix = single[a:b]
+                lg = self._prefill_group([ctxs[i] for i in ix], slots[ix])
+                if single.size == n:  # nothing shared: consecutive rows of the result
+                    out[a:b] = lg
+                else:
+                    out[torch.from_numpy(ix).to(self.device)] = lg
+                ngroups += 1
+            rows += int(lens[single].sum())
+        # holders: the master tail's rows into the first own page, the entry's logits into the slot's row
+        hold = np.nonzero(sh)[0]
+        if hold.size:
+            self._copy_tails(slots[hold])
+            out[torch.from_numpy(hold).to(self.device)] = torch.cat([kv.slot_entry[slots[i]].logits for i in hold])
+        self.last_prefill = {"rows": rows, "groups": ngroups, "shared": int(hold.size)}
         return out
 
-    def _prefill_group(self, ctxs: List[List[int]], slots: np.ndarray) -> torch.Tensor:
+    def _copy_tails(self, slots: np.ndarray) -> None:
+        """``ns_kv_copy_rows`` for the holders among ``slots`` whose shared context ends inside a page."""
+        from .. import _lib
+        from ..coder import _stream_handle
+
+        kv, s = self.kv, self.shape
+        src, dst, rows = kv.tail_copies(slots)
+        if src.size == 0:
+            return
+        d_src, d_dst, d_rows = (torch.from_numpy(x).to(self.device) for x in (src, dst, rows))
+        _check(_lib.lib().ns_kv_copy_rows(d_src.data_ptr(), d_dst.data_ptr(), d_rows.data_ptr(), int(src.size),
+                                          s.n_layer, kv.pool.layer_offset(1), s.n_head, s.n_embd // s.n_head,
+                                          self._kv_format, _stream_handle()), "ns_kv_copy_rows")
+
+    def _prefill_group(self, ctxs: List[List[int]], slots: np.ndarray, table: torch.Tensor = None) -> torch.Tensor:
+        """One ragged run of ``ctxs`` storing K/V through rows ``slots`` of ``table`` (default: the call's page
+        table); returns the logits after each context's last token."""
         from .. import _lib
         from ..coder import _stream_handle
 
@@ -474,7 +555,7 @@ class BatchedGPT2:
         d_start = torch.from_numpy(seq_start).to(dev)
         d_blocks = torch.from_numpy(blocks).to(dev)
         d_slot = torch.from_numpy(slots.astype(np.int32)).to(dev)
-        table = kv.table
+        table = kv.table if table is None else table
 
         def embed(h, a, lw0, eps):  # row positions = the token's index in its own context (% n_positions inside)
             _check(L.ns_lm_embed_ln_rows(tok.data_ptr(), self.wte.data_ptr(), self.wpe.data_ptr(), s.vocab,
@@ -485,8 +566,9 @@ class BatchedGPT2:
         def attention(i, qkv, o):
             _check(L.ns_seq_attention_ragged(qkv.data_ptr(), qkv.stride(0), o.data_ptr(), o.stride(0),
                                              d_start.data_ptr(), n, R, d_blocks.data_ptr(), blocks.shape[0], H, D,
-                                             1.0 / math.sqrt(D), table.data_ptr(), table.stride(0), kv.width,
-                                             d_slot.data_ptr(), kv.B, kv.pool.layer_offset(i), self._kv_format, st),
+                                             1.0 / math.sqrt(D), table.data_ptr(), table.stride(0), table.shape[1],
+                                             d_slot.data_ptr(), table.shape[0], kv.pool.layer_offset(i),
+                                             self._kv_format, st),
                    "ns_seq_attention_ragged")
 
         hs = self._rows_native(R, embed, attention)

@@ -20,6 +20,15 @@ stream and must be copied to grow; here a stream's rows live in pages it owns:
   use follows the live tokens, not B x the longest stream.  When the device has no room for another segment the
   pool reports it (:class:`KVCapacityError` upstream), never PyTorch's out-of-memory.
 
+SHARED CONTEXTS (library 0.30).  With one context per message, the messages of a call that carry the same context
+share its full pages read-only: a :class:`SharedContext` entry of the call's registry (``PagedKV.entries``, keyed by
+the trimmed context as a tuple) owns ``ceil(T / 32)`` pages -- the ``T // 32`` full ones and, when ``r = T % 32 > 0``,
+a MASTER TAIL page that no slot ever appends into.  A holder's table row has the entry's full pages in its first
+``T // 32`` columns and its own pages after them; the first own page receives the master tail's ``r`` rows as a copy
+(``ns_kv_copy_rows``), because the slot appends into that page from row ``r`` on.  :meth:`PagedKV.release` returns a
+slot's own pages only and drops its hold; the entry's pages go back to the pool with its last holder, and nothing is
+kept for later.  ``in_use`` / ``peak`` count physical pages (a shared page once); ``nch`` counts table columns.
+
 The host keeps a mirror of the table and of the lengths (every slot advances one position per step), so page
 bookkeeping needs no device read.  Pure host logic over torch tensors: the CPU tests drive it with CPU tensors.
 """
@@ -137,6 +146,52 @@ class KVPagePool:
         self.total = 0
 
 
+class SharedContext:
+    """One context's KV pages held by several slots of a call (see the module docstring): ``pages`` are its
+    ``ceil(T / 32)`` page addresses (the last one the master tail when ``tail_rows > 0``), ``logits`` the ``[1, ld]``
+    row after the context's last token (None until the entry has been prefilled), ``holders`` the slots holding it."""
+
+    __slots__ = ("key", "T", "pages", "full", "tail_rows", "logits", "holders")
+
+    def __init__(self, key, T: int, pages: np.ndarray):
+        self.key, self.T, self.pages = key, int(T), pages
+        self.full, self.tail_rows = self.T // PAGE_ROWS, self.T % PAGE_ROWS
+        self.logits = None
+        self.holders = 0
+
+
+def sharing_keys(contexts, entries=()):
+    """For every context of a call its registry key (the context as a tuple) if it shares -- another context of the
+    list equals it, or a live entry of ``entries`` holds it -- else None.  Only candidates (equal length, first, middle
+    and last id) are turned into tuples and hashed: a call of distinct contexts pays a few operations per context."""
+    def sig(c):
+        return (len(c), c[0], c[len(c) // 2], c[-1])
+
+    sigs = [sig(c) for c in contexts]
+    seen = {}
+    for g in sigs:
+        seen[g] = seen.get(g, 0) + 1
+    live = {sig(k) for k in entries}
+    keys = [tuple(c) if seen[g] > 1 or g in live else None for c, g in zip(contexts, sigs)]
+    count = {}
+    for k in keys:
+        if k is not None:
+            count[k] = count.get(k, 0) + 1
+    return [k if k is not None and (count[k] > 1 or k in entries) else None for k in keys]
+
+
+def shared_pages(T: int) -> int:
+    """Pages a shared context of ``T`` rows owns: its full pages and the master tail."""
+    return (int(T) + PAGE_ROWS - 1) // PAGE_ROWS
+
+
+def own_pages(T: int, ahead: int, shares: bool) -> int:
+    """Pages a message with a ``T``-row context maps for itself up to position ``T + ahead``: all of them, or, when it
+    shares the context, those after the context's full pages."""
+    need = (int(T) + int(ahead) + PAGE_ROWS - 1) // PAGE_ROWS
+    return need - int(T) // PAGE_ROWS if shares else need
+
+
 class PagedKV:
     """One call's page table, per-stream lengths and their host mirrors over a :class:`KVPagePool`.
 
@@ -155,8 +210,11 @@ class PagedKV:
         self.lens = torch.full((self.B,), self.T0, dtype=torch.int32, device=dev)
         self.lens_host = np.full(self.B, self.T0, dtype=np.int64)
         self.version = 0
-        self.in_use = 0  # pages mapped now, and the most ever mapped at once in this call
+        self.in_use = 0  # physical pages mapped now (a shared page once), and the most at once in this call
         self.peak = 0
+        self.entries = {}  # trimmed context (tuple) -> SharedContext, while at least one slot holds it
+        self.slot_entry: List[Optional[SharedContext]] = [None] * self.B
+        self.nshared = np.zeros(self.B, dtype=np.int64)  # leading table columns that are an entry's pages
 
     # ------------------------------------------------------------------
     def pages_in_use(self) -> int:
@@ -212,20 +270,86 @@ class PagedKV:
         dev = self.table.device
         self.table[torch.from_numpy(rows).to(dev), torch.from_numpy(cols).to(dev)] = torch.from_numpy(pages).to(dev)
 
+    def hold(self, slots, keys, lens) -> np.ndarray:
+        """Let every slot in ``slots`` (released, no page mapped) hold the shared context ``keys[i]`` of ``lens[i]``
+        rows: the entry is opened if no slot holds it yet (its pages taken from the pool; its ``logits`` stay None
+        until the caller has prefilled it), and its full pages become the slot's first table columns.  The slot's own
+        pages follow through :meth:`ensure`.  Returns the slots whose entry could not be opened (the pool is out of
+        memory); nothing is mapped for them."""
+        slots = np.asarray(slots, dtype=np.int64).reshape(-1)
+        failed, rows, cols, pages = [], [], [], []
+        for s, key, T in zip(slots.tolist(), keys, np.asarray(lens, dtype=np.int64).reshape(-1).tolist()):
+            if self.nch[s] or self.slot_entry[s] is not None:
+                raise RuntimeError("hold: the slot still has pages")
+            e = self.entries.get(key)
+            if e is None:
+                p = self.pool.take(shared_pages(T))
+                if p is None:
+                    failed.append(s)
+                    continue
+                e = self.entries[key] = SharedContext(key, T, p)
+                self.in_use += int(p.size)
+                self.peak = max(self.peak, self.in_use)
+            elif e.T != T:
+                raise ValueError("hold: the context's length differs from its entry's")
+            e.holders += 1
+            self.slot_entry[s] = e
+            self.nshared[s] = self.nch[s] = e.full
+            rows.append(np.full(e.full, s, dtype=np.int64))
+            cols.append(np.arange(e.full, dtype=np.int64))
+            pages.append(e.pages[: e.full])
+        if rows:
+            rows, cols, pages = np.concatenate(rows), np.concatenate(cols), np.concatenate(pages)
+            if rows.size:
+                if int(cols.max()) + 1 > self.width:
+                    self._grow_width(int(cols.max()) + 1)
+                self.host[rows, cols] = pages
+                dev = self.table.device
+                self.table[torch.from_numpy(rows).to(dev), torch.from_numpy(cols).to(dev)] = \
+                    torch.from_numpy(pages).to(dev)
+        return np.asarray(failed, dtype=np.int64)
+
+    def tail_copies(self, slots):
+        """``(src, dst, rows)`` for ``ns_kv_copy_rows``: for every holder in ``slots`` whose context ends inside a
+        page, the entry's master tail page, the slot's first own page (mapped) and the rows to copy."""
+        src, dst, rows = [], [], []
+        for s in np.asarray(slots, dtype=np.int64).reshape(-1).tolist():
+            e = self.slot_entry[s]
+            if e is None or e.tail_rows == 0:
+                continue
+            if self.nch[s] <= e.full:
+                raise RuntimeError("tail_copies: the holder's first own page is not mapped")
+            src.append(int(e.pages[e.full]))
+            dst.append(int(self.host[s, e.full]))
+            rows.append(e.tail_rows)
+        return (np.asarray(src, dtype=np.int64), np.asarray(dst, dtype=np.int64), np.asarray(rows, dtype=np.int32))
+
     def release(self, slots) -> None:
-        """Return the pages of ``slots`` to the pool and clear their table rows (the streams have ended)."""
+        """Return the own pages of ``slots`` to the pool and clear their table rows (the streams have ended); a slot
+        that held a shared context drops its hold, and the entry's pages follow its last holder."""
         slots = np.asarray(slots, dtype=np.int64).reshape(-1)
         if slots.size == 0:
             return
         n = int(self.nch[slots].max(initial=0))
         if n:
             pages = self.host[slots, :n]
-            pages = pages[pages != 0]
+            pages = pages[(pages != 0) & (np.arange(n)[None, :] >= self.nshared[slots][:, None])]
             self.pool.give(pages)
             self.in_use -= int(pages.size)
             self.host[slots, :n] = 0
             self.table[torch.from_numpy(slots).to(self.table.device), :n] = 0
         self.nch[slots] = 0
+        self.nshared[slots] = 0
+        for s in slots.tolist():
+            e = self.slot_entry[s]
+            if e is None:
+                continue
+            self.slot_entry[s] = None
+            e.holders -= 1
+            if e.holders == 0:  # nothing is kept for later: the page budget stays exact
+                self.pool.give(e.pages)
+                self.in_use -= int(e.pages.size)
+                del self.entries[e.key]
 
     def reset(self, slots, lens=None) -> None:
         """``release`` + the slots' cache lengths back to the shared context (a new message starts there), or to
@@ -259,7 +383,7 @@ class PagedKV:
 
     def compact(self, keep) -> None:
         """Keep only the slots ``keep`` (in that order) as rows 0..len(keep)-1; the other slots must have been
-        released.  Page tables move with their rows: no page is copied."""
+        released.  Page tables move with their rows, holds of shared contexts with them: no page is copied."""
         keep = np.asarray(keep, dtype=np.int64).reshape(-1)
         gone = np.setdiff1d(np.arange(self.B), keep)
         if gone.size and self.nch[gone].any():
@@ -268,5 +392,7 @@ class PagedKV:
         self.table = self.table.index_select(0, kt).contiguous()
         self.lens = self.lens.index_select(0, kt).contiguous()
         self.host, self.nch, self.lens_host = self.host[keep], self.nch[keep], self.lens_host[keep]
+        self.nshared = self.nshared[keep]
+        self.slot_entry = [self.slot_entry[i] for i in keep.tolist()]
         self.B = int(keep.size)
         self.version += 1

@@ -19,7 +19,9 @@ mean), so a lockstep batch spends its steps on finished streams.  Here messages 
 With ``contexts`` (one per message, library 0.29) there is no shared context: a slot starts at cache length 0, an
 admission maps the pages of each admitted message's own context plus its next steps, prefills those contexts ragged
 into the pages (``BatchedGPT2.prefill_contexts``, at the host check, outside the step graph) and puts each context's
-logits into its slot's row; an evicted message is prefilled again when it comes back.
+logits into its slot's row; an evicted message is prefilled again when it comes back.  Messages of the call that
+carry the same context (library 0.30) share its full KV pages: the context is prefilled once while any of them holds
+it, a holder maps only the pages after the context's full ones, and an evicted holder gives back only those.
 
 A stream's logits are bit-identical whatever the batch it runs in (the decode step is batch-invariant, including the
 paged attention), so a message's tokens are the same alone, in lockstep, or refilled into any slot.  Between host
@@ -111,20 +113,58 @@ def _trimmed(contexts, n: int) -> List[List[int]]:
     return ctxs
 
 
-def _admissible(queue, contexts, check_every: int, nslots: int, room: int) -> List[int]:
+def _multiplicity(contexts, share: bool):
+    """``(keys, shares)`` of a call's trimmed contexts: whether the message shares its context's pages -- more than
+    one message of the whole call carries it -- and then the context as a tuple, the key of its entry (else None)."""
+    from .kvpages import sharing_keys
+
+    keys = sharing_keys(contexts) if share else [None] * len(contexts)
+    return keys, [k is not None for k in keys]
+
+
+def _admissible(queue, contexts, check_every: int, nslots: int, room: int, keys=None, shares=None,
+                live=()) -> List[int]:
     """Pop the messages to admit now from the queue's front: at most ``nslots``, while the pages of their contexts
     and first ``check_every + 1`` positions fit in ``room`` pages (what the pool can still hand out beyond one page
-    per live slot).  The admission then maps exactly these pages."""
-    from .kvpages import PAGE_ROWS
+    per live slot).  The admission then maps exactly these pages.  A message that shares its context
+    (``shares[m]``, entry key ``keys[m]``) counts its own pages only -- those after the context's full pages -- and
+    its entry's pages once, with the first message of this batch that opens it, unless the entry is ``live``."""
+    from .kvpages import own_pages, shared_pages
 
-    out, used = [], 0
+    out, used, opened = [], 0, set()
     while queue and len(out) < nslots:
-        need = (len(contexts[queue[0]]) + check_every + 1 + PAGE_ROWS - 1) // PAGE_ROWS
+        m = queue[0]
+        T = len(contexts[m])
+        sh = shares is not None and shares[m]
+        need = own_pages(T, check_every + 1, sh)
+        opens = sh and keys[m] not in live and keys[m] not in opened
+        if opens:
+            need += shared_pages(T)
         if used + need > room:
             break
         used += need
+        if opens:
+            opened.add(keys[m])
         out.append(queue.popleft())
     return out
+
+
+def _map_contexts(kv, slots, keys, shares, tl, upto) -> np.ndarray:
+    """Page mapping of an admission with per-message contexts: every slot in ``slots`` starts over at its context's
+    length ``tl``, a sharing message holds its context's entry (opened here if it is not live), and every message
+    gets its own pages for the positions below ``upto``.  Returns the mask of the slots that were served; the others
+    are left released (the pool is out of memory)."""
+    kv.reset(slots, lens=tl)
+    sh = np.asarray(shares, dtype=bool)
+    failed = set()
+    if sh.any():
+        failed = set(kv.hold(slots[sh], [k for k, f in zip(keys, sh) if f], tl[sh]).tolist())
+    rest = np.asarray([s not in failed for s in slots.tolist()], dtype=bool)
+    failed |= set(kv.ensure(slots[rest], upto[rest]).tolist())
+    ok = np.asarray([s not in failed for s in slots.tolist()], dtype=bool)
+    if not ok.all():
+        kv.reset(slots[~ok])
+    return ok
 
 
 class SlotEncoder:
@@ -133,7 +173,7 @@ class SlotEncoder:
     def __init__(self, provider, ctx, bit_lists: Sequence[Sequence[int]], context: Sequence[int], *, slots: int,
                  finish: bool, stop_text: Optional[str], stats: bool, check_every: int, stall_steps: int,
                  hard_cap: int, use_graph: bool, compact: bool = True,
-                 contexts: Optional[Sequence[Sequence[int]]] = None):
+                 contexts: Optional[Sequence[Sequence[int]]] = None, share: bool = True):
         self.p, self.lm, self.ctx = provider, provider.lm, ctx
         self.bits = bit_lists
         self.N = len(bit_lists)
@@ -142,6 +182,9 @@ class SlotEncoder:
         # one context per message (``context`` is then None): every admission prefills the admitted messages'
         # contexts into their slots' own pages (``BatchedGPT2.prefill_contexts``), no shared prefix
         self.contexts = _trimmed(contexts, self.N) if contexts is not None else None
+        # messages of the call with equal contexts share the context's KV pages (lm/kvpages.py)
+        self.keys, self.shares = _multiplicity(self.contexts, share) if contexts is not None else (None, None)
+        self.prefill_shared = 0
         self.ctx_len = np.zeros(self.S, dtype=np.int64)  # context rows of the message in each slot (per-context)
         self.prefill_rows = 0
         self.prefill_groups = 0
@@ -274,7 +317,8 @@ class SlotEncoder:
                     if queue and empty.size and not admit_blocked:
                         room = lm.pool.free_pages + lm.pool.growable_pages() - int(live.sum()) - 1
                         if per_ctx:
-                            ms = _admissible(queue, self.contexts, self.check_every, empty.size, room)
+                            ms = _admissible(queue, self.contexts, self.check_every, empty.size, room, self.keys,
+                                             self.shares, lm.kv.entries)
                             if ms:
                                 back = self._admit_contexts(sess, logits, empty[:len(ms)], ms, slot_msg, last_pos,
                                                             last_move, t)
@@ -373,18 +417,16 @@ class SlotEncoder:
         lm = self.lm
         slots = np.asarray(slots, dtype=np.int64)
         tl = np.asarray([len(self.contexts[m]) for m in msgs], dtype=np.int64)
-        lm.kv.reset(slots, lens=tl)
-        failed = set(lm.kv.ensure(slots, tl + self.check_every + 1).tolist())
-        ok = np.asarray([s not in failed for s in slots.tolist()], dtype=bool)
+        ok = _map_contexts(lm.kv, slots, [self.keys[m] for m in msgs], [self.shares[m] for m in msgs], tl,
+                           tl + self.check_every + 1)
         back = [m for m, k in zip(msgs, ok) if not k]
-        if not ok.all():
-            lm.kv.reset(slots[~ok])
         slots, msgs = slots[ok], [m for m, k in zip(msgs, ok) if k]
         if not msgs:
             return back
-        first = lm.prefill_contexts([self.contexts[m] for m in msgs], slots)
+        first = lm.prefill_contexts([self.contexts[m] for m in msgs], slots, [self.shares[m] for m in msgs])
         self.prefill_rows += lm.last_prefill["rows"]
         self.prefill_groups += lm.last_prefill["groups"]
+        self.prefill_shared += lm.last_prefill["shared"]
         sess.load_slots(slots, [self.bits[m] for m in msgs])
         idx = torch.as_tensor(slots, device=logits.device)
         logits.index_copy_(0, idx, first.to(logits.dtype))
@@ -437,13 +479,15 @@ class SlotDecoder:
 
     def __init__(self, provider, ctx, token_lists: Sequence[Sequence[int]], context: Sequence[int], *, slots: int,
                  use_graph: bool, check_every: int = 16, compact: bool = True,
-                 contexts: Optional[Sequence[Sequence[int]]] = None):
+                 contexts: Optional[Sequence[Sequence[int]]] = None, share: bool = True):
         self.p, self.lm, self.ctx = provider, provider.lm, ctx
         self.lists = token_lists
         self.N = len(token_lists)
         self.S = max(1, min(int(slots), self.N))
         self.context = context
         self.contexts = _trimmed(contexts, self.N) if contexts is not None else None  # one per message
+        self.keys, self.shares = _multiplicity(self.contexts, share) if contexts is not None else (None, None)
+        self.prefill_shared = 0
         self.prefill_rows = 0
         self.prefill_groups = 0
         self.use_graph, self.check_every, self.allow_compact = use_graph, int(check_every), compact
@@ -555,7 +599,8 @@ class SlotDecoder:
                     if queue and empty.size and not admit_blocked:
                         room = lm.pool.free_pages + lm.pool.growable_pages() - int(live.sum()) - 1
                         if per_ctx:
-                            adm_m = _admissible(queue, self.contexts, self.check_every, empty.size, room)
+                            adm_m = _admissible(queue, self.contexts, self.check_every, empty.size, room,
+                                                self.keys, self.shares, lm.kv.entries)
                             if adm_m:
                                 back = self._admit_contexts(st, logits, init_row, empty[:len(adm_m)], adm_m, slot_msg,
                                                             nlen_host, ctx_host, Tcap)
@@ -646,18 +691,16 @@ class SlotDecoder:
         slots = np.asarray(slots, dtype=np.int64)
         tl = np.asarray([len(self.contexts[m]) for m in msgs], dtype=np.int64)
         nl = np.asarray([len(self.lists[m]) for m in msgs], dtype=np.int64)
-        lm.kv.reset(slots, lens=tl)
-        failed = set(lm.kv.ensure(slots, tl + np.minimum(self.check_every + 1, nl)).tolist())
-        ok = np.asarray([s not in failed for s in slots.tolist()], dtype=bool)
+        ok = _map_contexts(lm.kv, slots, [self.keys[m] for m in msgs], [self.shares[m] for m in msgs], tl,
+                           tl + np.minimum(self.check_every + 1, nl))
         back = [m for m, k in zip(msgs, ok) if not k]
-        if not ok.all():
-            lm.kv.reset(slots[~ok])
         slots, msgs, tl = slots[ok], [m for m, k in zip(msgs, ok) if k], tl[ok]
         if not msgs:
             return back
-        first = lm.prefill_contexts([self.contexts[m] for m in msgs], slots)
+        first = lm.prefill_contexts([self.contexts[m] for m in msgs], slots, [self.shares[m] for m in msgs])
         self.prefill_rows += lm.last_prefill["rows"]
         self.prefill_groups += lm.last_prefill["groups"]
+        self.prefill_shared += lm.last_prefill["shared"]
         idx = torch.as_tensor(slots, device=logits.device)
         st["ctx"][idx] = torch.from_numpy(tl.astype(np.int32)).to(logits.device)
         ctx_host[slots] = tl
