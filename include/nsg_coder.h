@@ -104,7 +104,8 @@ int ns_max_topk(int logits_dtype);
  * automatic). */
 int ns_set_split_max_batch(int max_batch);
 
-/* Reset B stream states to [0, 2^precision), bit_pos 0. */
+/* Reset B stream states to [0, 2^precision), bit_pos 0 (with a quality table registered: 2^precision of each
+ * stream's row). */
 int ns_init_state(ns_ctx* ctx, ns_stream_state* d_state, int B, void* hip_stream);
 
 /* One encode step for streams [0,B).  d_logits: [B, ld] row-major, 16-byte aligned, ld a multiple of
@@ -216,6 +217,37 @@ int ns_set_rank_rows(ns_ctx* ctx, const int32_t* d_count, const int32_t* d_idmap
  * elsewhere.  d_scratch_state: [B] states the call may overwrite. */
 int ns_token_probs(ns_ctx* ctx, const void* d_logits, int64_t ld, int B, double temp, const ns_rank_quality* quality,
                    double* d_probs, int64_t probs_stride, ns_stream_state* d_scratch_state, void* hip_stream);
+
+/* Per-stream coder quality: what one stream's step derives from (temp, topk, precision), the per-message
+ * `quality` of the reference's stego_encode / encode_arithmetic (code_base/arithmetic.py:78-88).  One row per
+ * stream in DEVICE memory; rows are produced on the host by ns_stream_quality_fill and copied there by the caller
+ * (no kernel writes the table).  The layout is fixed: 32 bytes, fields at the offsets below. */
+typedef struct ns_stream_quality {
+    double inv_temp;   /*  0: 1 / temp                                                    */
+    float c32;         /*  8: (float)(inv_temp * log2(e)), the fast-sum exponent scale    */
+    int32_t topk;      /* 12: topk as given                                               */
+    int32_t K;         /* 16: min(topk, valid ids)                                        */
+    int32_t precision; /* 20: interval bits, 1..60                                        */
+    int32_t spec_j;    /* 24: speculative threshold rank in the sample (0: no sample)     */
+    int32_t reserved;  /* 28: 0                                                           */
+} ns_stream_quality;
+#define NS_STREAM_QUALITY_BYTES 32
+
+/* Fill one row on the host (pure arithmetic: no device, no context).  banned: HOST array as in ns_encode_step.
+ * k_max is the largest topk of the call the row will take part in (ns_set_stream_quality): the speculative
+ * sample is on for every row of a call or for none, so spec_j is 0 when the rule switches the sample off at
+ * k_max.  NS_ERR_CONFIG unless temp > 0, 1 <= topk <= k_max, 1 <= precision <= 60, vocab leaves two valid ids. */
+int ns_stream_quality_fill(int vocab, const int32_t* banned, int nbanned, double temp, int topk, int precision,
+                           int k_max, ns_stream_quality* out_row);
+
+/* Register (NULL: clear) a DEVICE table with one row per stream of the later steps; the caller keeps it alive.
+ * While registered, ns_encode_step / ns_decode_step / ns_init_state take stream b's temp, topk and precision from
+ * row b (the calls' temp / topk arguments and the context's precision are ignored) and every host decision --
+ * the rank-slot bucket, the split or wave-per-stream form, the sample -- follows k_max alone, so a captured step
+ * stays valid whatever the rows hold.  Every row must have been filled with this k_max and K <= k_max.
+ * k_max > ns_max_topk(dtype) (the wide path): NS_ERR_UNSUPPORTED.  ns_sample_step, the rank steps and
+ * ns_token_probs return NS_ERR_CONFIG while a table is registered. */
+int ns_set_stream_quality(ns_ctx* ctx, const ns_stream_quality* d_table, int k_max);
 
 /* Rare-event diagnostics, cumulative since ns_create: counters[0] = stream-steps that took the exact-sum
  * path, counters[1] = candidate-buffer overflow compactions, counters[2] = speculative-threshold misses

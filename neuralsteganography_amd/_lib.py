@@ -29,6 +29,7 @@ EXPORTS = ("ns_create", "ns_destroy", "ns_last_error", "ns_version", "ns_max_top
            "ns_init_state",
            "ns_encode_step", "ns_decode_step", "ns_set_sentence_end", "ns_set_stats", "ns_sample_step", "ns_set_rank_export",
            "ns_rank_encode_step", "ns_set_rank_rows", "ns_rank_decode_step", "ns_token_probs",
+           "ns_stream_quality_fill", "ns_set_stream_quality",
            "ns_read_counters", "ns_decode_attention", "ns_decode_attention_dev", "ns_decode_attention_prefix",
            "ns_decode_attention_fp8", "ns_decode_attention_ex", "ns_quantize_fp8",
            "ns_score_rows", "ns_lm_gemm", "ns_lm_gemm_config", "ns_lm_gemm_configs", "ns_lm_layernorm",
@@ -67,6 +68,18 @@ class NsRankQuality(ctypes.Structure):
 
     _fields_ = [("top_k", ctypes.c_int32), ("cap_bits", ctypes.c_int32), ("top_p", ctypes.c_double),
                 ("min_prob", ctypes.c_double), ("prob_temp", ctypes.c_double)]
+
+
+class NsStreamQuality(ctypes.Structure):
+    """``ns_stream_quality`` (include/nsg_coder.h): one stream's coder quality as the step kernel reads it."""
+
+    _fields_ = [("inv_temp", ctypes.c_double), ("c32", ctypes.c_float), ("topk", ctypes.c_int32),
+                ("K", ctypes.c_int32), ("precision", ctypes.c_int32), ("spec_j", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+NS_STREAM_QUALITY_BYTES = 32
+assert ctypes.sizeof(NsStreamQuality) == NS_STREAM_QUALITY_BYTES
 
 
 def lib() -> ctypes.CDLL:
@@ -116,6 +129,11 @@ def lib() -> ctypes.CDLL:
     L.ns_set_rank_rows.argtypes = [vp, vp, vp, ctypes.c_int64, ctypes.c_int]
     L.ns_set_rank_export.restype = ctypes.c_int
     L.ns_set_rank_export.argtypes = [vp, vp, ctypes.c_int]
+    L.ns_stream_quality_fill.restype = ctypes.c_int
+    L.ns_stream_quality_fill.argtypes = [ctypes.c_int, i32p, ctypes.c_int, ctypes.c_double, ctypes.c_int,
+                                         ctypes.c_int, ctypes.c_int, ctypes.POINTER(NsStreamQuality)]
+    L.ns_set_stream_quality.restype = ctypes.c_int
+    L.ns_set_stream_quality.argtypes = [vp, vp, ctypes.c_int]
     L.ns_set_stats.restype = ctypes.c_int
     L.ns_set_stats.argtypes = [vp, vp]
     L.ns_sample_step.restype = ctypes.c_int

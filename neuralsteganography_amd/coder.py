@@ -89,6 +89,97 @@ class CoderParams:
             raise ConfigurationError(f"at most {_lib.NS_MAX_BANNED} banned ids")
 
 
+class StreamQuality:
+    """Per-stream coder quality rows (``ns_stream_quality``) for one call: row i is what the step kernel derives
+    from ``params[i]`` (temp, topk, precision), filled by ``ns_stream_quality_fill`` -- the derived values, the
+    speculative-sample rule included, live in the library only.  ``k_max`` (default: the largest topk) is the
+    value every launch decision of the call follows; all rows share vocab, dtype and banned ids."""
+
+    def __init__(self, params: Sequence[CoderParams], k_max: Optional[int] = None):
+        params = list(params)
+        if not params:
+            raise ConfigurationError("StreamQuality needs at least one stream")
+        head = params[0]
+        for q in params:
+            q.validate()
+            if (q.vocab, q.dtype, q.banned_ids()) != (head.vocab, head.dtype, head.banned_ids()):
+                raise ConfigurationError("the streams of one call share vocab, logits dtype and banned ids")
+        self.params = params
+        self.k_max = int(k_max) if k_max is not None else max(q.topk for q in params)
+        ban = head.banned_ids()
+        cban = (ctypes.c_int32 * max(1, len(ban)))(*ban)
+        rows = (_lib.NsStreamQuality * len(params))()
+        L = _lib.lib()
+        for i, q in enumerate(params):
+            rc = L.ns_stream_quality_fill(q.vocab, cban, len(ban), float(q.temp), int(q.topk), int(q.precision),
+                                          self.k_max, ctypes.byref(rows[i]))
+            if rc != _lib.NS_OK:
+                raise ConfigurationError(f"stream {i}: {L.ns_last_error(None).decode()}")
+        # [n, 4] int64: the 32-byte rows as the device table holds them (indexable like the state rows)
+        self.rows = np.frombuffer(bytes(rows), dtype=np.int64).reshape(len(params), 4).copy()
+        self.precisions = np.asarray([q.precision for q in params], dtype=np.int64)
+
+    def __len__(self) -> int:
+        return len(self.params)
+
+    @property
+    def max_precision(self) -> int:
+        return int(self.precisions.max())
+
+    def take(self, idx: Sequence[int]) -> "StreamQuality":
+        """The rows of streams ``idx`` (same ``k_max``: rows are only valid for the call they were filled for)."""
+        idx = np.asarray(idx, dtype=np.int64)
+        out = StreamQuality.__new__(StreamQuality)
+        out.params = [self.params[int(i)] for i in idx]
+        out.k_max = self.k_max
+        out.rows, out.precisions = self.rows[idx].copy(), self.precisions[idx].copy()
+        return out
+
+    def context_params(self) -> CoderParams:
+        """Parameters of the coder context that serves the call: topk ``k_max`` and the largest precision (with a
+        table registered the kernel reads neither, nor the temperature, from the context)."""
+        head = self.params[0]
+        return CoderParams(vocab=head.vocab, precision=self.max_precision, temp=1.0, topk=self.k_max, dtype=head.dtype,
+                           banned=head.banned)
+
+    def table(self, device):
+        torch = _torch()
+        return torch.from_numpy(self.rows).to(device)
+
+    def init_rows(self, device):
+        """[n, 4] int64 fresh coder states, ``hi = 2^precision`` of each row."""
+        torch = _torch()
+        st = np.zeros((len(self.precisions), 4), dtype=np.int64)
+        st[:, 1] = np.left_shift(np.int64(1), self.precisions)
+        return torch.from_numpy(st).to(device)
+
+
+def _check_quality(ctx: "CoderContext", B: int, quality: Optional[StreamQuality]) -> None:
+    if quality is None:
+        return
+    if len(quality) != B:
+        raise ConfigurationError(f"{len(quality)} quality rows for {B} streams")
+    if quality.k_max > ctx.params.topk:
+        raise ConfigurationError("the coder context's topk must cover the quality table's k_max")
+
+
+class _table_registered:
+    """``ns_set_stream_quality`` around a call (None: nothing to do), cleared on exit like ``ns_set_stats``."""
+
+    def __init__(self, ctx: "CoderContext", table, k_max: int):
+        self.ctx, self.table, self.k_max = ctx, table, k_max
+
+    def __enter__(self):
+        if self.table is not None:
+            self.ctx.check(_lib.lib().ns_set_stream_quality(self.ctx._h, _ptr(self.table), int(self.k_max)),
+                           "ns_set_stream_quality")
+
+    def __exit__(self, *exc):
+        if self.table is not None and self.ctx._h:
+            _lib.lib().ns_set_stream_quality(self.ctx._h, ctypes.c_void_p(0), 0)
+        return False
+
+
 _DEFERRED: List[tuple] = []  # (device, handle) of contexts closed during a graph capture
 
 
@@ -285,13 +376,18 @@ class EncodeSession:
     tolerance of the reference, not bit-exact -- at the cost of a heavier kernel build."""
 
     def __init__(self, ctx: CoderContext, payload_bits: Sequence[Sequence[int]], max_tokens: Optional[int] = None,
-                 stats: bool = False, payload_stride: Optional[int] = None):
+                 stats: bool = False, payload_stride: Optional[int] = None,
+                 quality: Optional[StreamQuality] = None):
         torch = _torch()
         self.ctx = ctx
         self.B = len(payload_bits)
         if self.B < 1 or self.B > ctx.max_batch:
             raise ConfigurationError(f"batch {self.B} outside [1, {ctx.max_batch}]")
+        _check_quality(ctx, self.B, quality)
         dev = torch.device("cuda", ctx.device)
+        # per-stream quality rows (None: the context's one quality for every stream), [B, 4] int64 = 32-byte rows
+        self.qtable = quality.table(dev) if quality is not None else None
+        self.k_max = quality.k_max if quality is not None else 0
         self.nbits_host = np.asarray([len(b) for b in payload_bits], dtype=np.int64)
         stride = max(1, int((self.nbits_host.max() + 7) // 8), int(payload_stride or 0))
         pl = np.zeros((self.B, stride), dtype=np.uint8)
@@ -302,7 +398,8 @@ class EncodeSession:
         self.payload = torch.from_numpy(pl).to(dev)
         self.nbits = torch.from_numpy(self.nbits_host).to(dev)
         self.state = _state_tensor(self.B, dev)
-        ctx.check(_lib.lib().ns_init_state(ctx._h, _ptr(self.state), self.B, _stream_handle()), "ns_init_state")
+        with _table_registered(ctx, self.qtable, self.k_max):
+            ctx.check(_lib.lib().ns_init_state(ctx._h, _ptr(self.state), self.B, _stream_handle()), "ns_init_state")
         self.out_token = torch.zeros(self.B, dtype=torch.int32, device=dev)
         cap = max_tokens if max_tokens is not None else int(2 * self.nbits_host.max() + 64)
         self.hist = torch.full((self.B, cap), -1, dtype=torch.int32, device=dev)
@@ -335,11 +432,12 @@ class EncodeSession:
         L = _lib.lib()
         if self.stats_acc is not None:
             self.ctx.check(L.ns_set_stats(self.ctx._h, _ptr(self.stats_acc)), "ns_set_stats")
-        rc = L.ns_encode_step(
-            self.ctx._h, _ptr(logits), logits.stride(0), self.B, _ptr(self.payload), self.payload.stride(0),
-            _ptr(self.nbits), _ptr(self.state), _ptr(self.out_token), _ptr(self.hist), self.hist.shape[1],
-            float(p.temp), int(p.topk), self.ctx._banned, self.ctx._nbanned, _ptr(self.trace), flags,
-            _stream_handle())
+        with _table_registered(self.ctx, self.qtable, self.k_max):
+            rc = L.ns_encode_step(
+                self.ctx._h, _ptr(logits), logits.stride(0), self.B, _ptr(self.payload), self.payload.stride(0),
+                _ptr(self.nbits), _ptr(self.state), _ptr(self.out_token), _ptr(self.hist), self.hist.shape[1],
+                float(p.temp), int(p.topk), self.ctx._banned, self.ctx._nbanned, _ptr(self.trace), flags,
+                _stream_handle())
         if self.stats_acc is not None:
             L.ns_set_stats(self.ctx._h, ctypes.c_void_p(0))
         self.ctx.check(rc, "ns_encode_step")
@@ -374,10 +472,13 @@ class EncodeSession:
         return _state_fields(self.state)
 
     # ---------------------------------------------------------------- slots (lm/slots.py: refill, compaction)
-    def load_slots(self, slots: Sequence[int], payload_bits: Sequence[Sequence[int]]) -> None:
+    def load_slots(self, slots: Sequence[int], payload_bits: Sequence[Sequence[int]],
+                   quality: Optional[StreamQuality] = None) -> None:
         """Start new payloads in ``slots`` (rows of this session): payload row, bit count, a fresh coder state
         (``ns_init_state``'s values) and, with stats, zeroed accumulators.  The token history row is reused from
-        position 0 (only the first ``ntokens`` entries of a row are ever read)."""
+        position 0 (only the first ``ntokens`` entries of a row are ever read).  A session with per-stream quality
+        takes the admitted streams' rows in ``quality`` (filled for the session's ``k_max``): the table rows are
+        written with the payload, and each fresh state starts at its row's ``2^precision``."""
         torch = _torch()
         n = len(slots)
         if n == 0:
@@ -397,17 +498,28 @@ class EncodeSession:
         self.payload[idx] = torch.from_numpy(pl).to(dev)
         self.nbits[idx] = torch.from_numpy(nb).to(dev)
         self.nbits_host[np.asarray(slots)] = nb
-        self.state[idx] = self.init_row().expand(n, 4)
+        if (quality is None) != (self.qtable is None):
+            raise ConfigurationError("load_slots: quality rows go with a session created with per-stream quality")
+        if quality is not None:
+            if len(quality) != n or quality.k_max != self.k_max:
+                raise ConfigurationError("load_slots: one quality row per slot, filled for the session's k_max")
+            self.qtable[idx] = quality.table(dev)
+            self.state[idx] = quality.init_rows(dev)
+        else:
+            self.state[idx] = self.init_row().expand(n, 4)
         if self.stats_acc is not None:
             self.stats_acc[idx] = 0
 
-    def init_row(self):
-        """[1, 4] int64: the state ``ns_init_state`` writes (lo 0, hi 2^precision, bit_pos 0, ntokens | flags 0)."""
+    def init_row(self, precision: Optional[int] = None):
+        """[1, 4] int64: the state ``ns_init_state`` writes (lo 0, hi 2^precision, bit_pos 0, ntokens | flags 0);
+        ``precision``: that of the stream's quality row (default: the context's)."""
         torch = _torch()
-        return torch.tensor([[0, 1 << self.ctx.params.precision, 0, 0]], dtype=torch.int64, device=self.state.device)
+        P = self.ctx.params.precision if precision is None else int(precision)
+        return torch.tensor([[0, 1 << P, 0, 0]], dtype=torch.int64, device=self.state.device)
 
     def park_slots(self, slots: Sequence[int]) -> None:
-        """Mark ``slots`` finished (NS_ST_DONE): the coder step and the decode attention skip them (empty slots)."""
+        """Mark ``slots`` finished (NS_ST_DONE): the coder step and the decode attention skip them (empty slots;
+        their quality rows stay as they are -- a finished stream's row is never read)."""
         if len(slots) == 0:
             return
         torch = _torch()
@@ -419,7 +531,7 @@ class EncodeSession:
         """Keep rows ``keep`` (in that order) of every per-stream buffer: the session now has len(keep) streams."""
         torch = _torch()
         idx = torch.as_tensor(np.asarray(keep, dtype=np.int64), device=self.state.device)
-        for name in ("payload", "nbits", "state", "out_token", "hist", "stats_acc", "trace"):
+        for name in ("payload", "nbits", "state", "out_token", "hist", "stats_acc", "trace", "qtable"):
             t = getattr(self, name)
             if t is not None:
                 setattr(self, name, t.index_select(0, idx).contiguous())
@@ -450,13 +562,17 @@ class EncodeSession:
 class DecodeSession:
     """B received token streams (ragged) being decoded back to bits."""
 
-    def __init__(self, ctx: CoderContext, token_lists: Sequence[Sequence[int]]):
+    def __init__(self, ctx: CoderContext, token_lists: Sequence[Sequence[int]],
+                 quality: Optional[StreamQuality] = None):
         torch = _torch()
         self.ctx = ctx
         self.B = len(token_lists)
         if self.B < 1 or self.B > ctx.max_batch:
             raise ConfigurationError(f"batch {self.B} outside [1, {ctx.max_batch}]")
+        _check_quality(ctx, self.B, quality)
         dev = torch.device("cuda", ctx.device)
+        self.qtable = quality.table(dev) if quality is not None else None
+        self.k_max = quality.k_max if quality is not None else 0
         self.lens = np.asarray([len(t) for t in token_lists], dtype=np.int64)
         self.T = int(self.lens.max(initial=0))
         tok = np.zeros((max(self.T, 1), self.B), dtype=np.int32)
@@ -471,11 +587,12 @@ class DecodeSession:
         self.tok = torch.from_numpy(tok).to(dev)
         self.last = torch.from_numpy(last).to(dev)
         self.act = torch.from_numpy(act).to(dev)
-        P = ctx.params.precision
+        P = quality.max_precision if quality is not None else ctx.params.precision  # the call's largest
         self.out_stride = int((self.T * P + P + 7) // 8 + 8)
         self.out_bits = torch.zeros((self.B, self.out_stride), dtype=torch.uint8, device=dev)
         self.state = _state_tensor(self.B, dev)
-        ctx.check(_lib.lib().ns_init_state(ctx._h, _ptr(self.state), self.B, _stream_handle()), "ns_init_state")
+        with _table_registered(ctx, self.qtable, self.k_max):
+            ctx.check(_lib.lib().ns_init_state(ctx._h, _ptr(self.state), self.B, _stream_handle()), "ns_init_state")
         self.trace = None
         self.t = 0
 
@@ -491,10 +608,11 @@ class DecodeSession:
         t = self.t
         _check_logits(self.ctx, self.B, logits)
         flags = _lib.NS_STEP_FORCE_EXACT_SUM if force_exact else 0
-        rc = _lib.lib().ns_decode_step(
-            self.ctx._h, _ptr(logits), logits.stride(0), self.B, _ptr(self.tok[t]), _ptr(self.last[t]),
-            _ptr(self.act[t]), _ptr(self.state), _ptr(self.out_bits), self.out_stride, float(p.temp),
-            int(p.topk), self.ctx._banned, self.ctx._nbanned, _ptr(self.trace), flags, _stream_handle())
+        with _table_registered(self.ctx, self.qtable, self.k_max):
+            rc = _lib.lib().ns_decode_step(
+                self.ctx._h, _ptr(logits), logits.stride(0), self.B, _ptr(self.tok[t]), _ptr(self.last[t]),
+                _ptr(self.act[t]), _ptr(self.state), _ptr(self.out_bits), self.out_stride, float(p.temp),
+                int(p.topk), self.ctx._banned, self.ctx._nbanned, _ptr(self.trace), flags, _stream_handle())
         self.ctx.check(rc, "ns_decode_step")
         self.t += 1
 
@@ -514,10 +632,11 @@ class DecodeSession:
         torch.index_select(self.act, 0, self.d_t, out=self.act_s)
         p = self.ctx.params
         flags = _lib.NS_STEP_FORCE_EXACT_SUM if force_exact else 0
-        rc = _lib.lib().ns_decode_step(
-            self.ctx._h, _ptr(logits), logits.stride(0), self.B, _ptr(self.tok_s), _ptr(self.last_s),
-            _ptr(self.act_s), _ptr(self.state), _ptr(self.out_bits), self.out_stride, float(p.temp),
-            int(p.topk), self.ctx._banned, self.ctx._nbanned, _ptr(self.trace), flags, _stream_handle())
+        with _table_registered(self.ctx, self.qtable, self.k_max):
+            rc = _lib.lib().ns_decode_step(
+                self.ctx._h, _ptr(logits), logits.stride(0), self.B, _ptr(self.tok_s), _ptr(self.last_s),
+                _ptr(self.act_s), _ptr(self.state), _ptr(self.out_bits), self.out_stride, float(p.temp),
+                int(p.topk), self.ctx._banned, self.ctx._nbanned, _ptr(self.trace), flags, _stream_handle())
         self.ctx.check(rc, "ns_decode_step")
         self.d_t += 1
         return self.tok_s[0]
@@ -532,11 +651,12 @@ class DecodeSession:
 
 def encode_batch(ctx: CoderContext, payload_bits: Sequence[Sequence[int]], logits_fn, *, max_steps: int = 1 << 20,
                  check_every: int = 32, force_exact: bool = False, finish_sent: bool = False,
-                 return_stats: bool = False):
+                 return_stats: bool = False, quality: Optional[StreamQuality] = None):
     """Run encode steps until every stream has consumed its payload; ``logits_fn(step, last_tokens)``
     returns the ``[B, ld]`` logits of that step.  ``return_stats=True`` returns ``(tokens, stats)`` with the
-    per-stream statistics of ``encode_arithmetic`` (see :meth:`EncodeSession.stats`)."""
-    sess = EncodeSession(ctx, payload_bits, stats=return_stats)
+    per-stream statistics of ``encode_arithmetic`` (see :meth:`EncodeSession.stats`).  ``quality``: one row per
+    stream (:class:`StreamQuality`) instead of the context's one quality."""
+    sess = EncodeSession(ctx, payload_bits, stats=return_stats, quality=quality)
     last = sess.out_token
     for t in range(max_steps):
         if t % check_every == 0:
@@ -552,8 +672,8 @@ def encode_batch(ctx: CoderContext, payload_bits: Sequence[Sequence[int]], logit
 
 
 def decode_batch(ctx: CoderContext, token_lists: Sequence[Sequence[int]], logits_fn, *,
-                 force_exact: bool = False) -> List[List[int]]:
-    sess = DecodeSession(ctx, token_lists)
+                 force_exact: bool = False, quality: Optional[StreamQuality] = None) -> List[List[int]]:
+    sess = DecodeSession(ctx, token_lists, quality=quality)
     for t in range(sess.T):
         sess.step(logits_fn(t, sess.tok[t]), force_exact=force_exact)
     return sess.bits()
@@ -636,18 +756,22 @@ class StreamingDecodeSession:
     tokens).  A stream whose token falls outside the kept top-k' is flagged NS_ST_ERR_DIVERGE with its state
     untouched and its ranked kept ids exported; :meth:`clear` re-arms it for a re-issued step."""
 
-    def __init__(self, ctx: CoderContext, B: int, max_tokens: int):
+    def __init__(self, ctx: CoderContext, B: int, max_tokens: int, quality: Optional[StreamQuality] = None):
         torch = _torch()
         if B < 1 or B > ctx.max_batch:
             raise ConfigurationError(f"batch {B} outside [1, {ctx.max_batch}]")
         self.ctx, self.B = ctx, int(B)
+        _check_quality(ctx, self.B, quality)
         dev = torch.device("cuda", ctx.device)
         self.dev = dev
-        P = ctx.params.precision
+        self.qtable = quality.table(dev) if quality is not None else None
+        self.k_max = quality.k_max if quality is not None else 0
+        P = self.P = quality.max_precision if quality is not None else ctx.params.precision
         self.out_stride = int((max(1, max_tokens) * P + P + 7) // 8 + 8)
         self.out_bits = torch.zeros((self.B, self.out_stride), dtype=torch.uint8, device=dev)
         self.state = _state_tensor(self.B, dev)
-        ctx.check(_lib.lib().ns_init_state(ctx._h, _ptr(self.state), self.B, _stream_handle()), "ns_init_state")
+        with _table_registered(ctx, self.qtable, self.k_max):
+            ctx.check(_lib.lib().ns_init_state(ctx._h, _ptr(self.state), self.B, _stream_handle()), "ns_init_state")
         self.rank_stride = int(ctx.K) + 1
         self.ranked = torch.full((self.B, self.rank_stride), -1, dtype=torch.int32, device=dev)
 
@@ -665,15 +789,16 @@ class StreamingDecodeSession:
         p = self.ctx.params
         _check_logits(self.ctx, self.B, logits)
         f = _state_fields(self.state)
-        self._grow(int(f["bit_pos"].max(initial=0)) + 2 * p.precision)
+        self._grow(int(f["bit_pos"].max(initial=0)) + 2 * self.P)
         tok = torch.tensor(np.asarray(tokens, dtype=np.int32), device=self.dev)
         last = torch.tensor(np.asarray(is_last, dtype=np.uint8), device=self.dev)
         act = torch.tensor(np.asarray(active, dtype=np.uint8), device=self.dev)
         L = _lib.lib()
         self.ctx.check(L.ns_set_rank_export(self.ctx._h, _ptr(self.ranked), self.rank_stride), "ns_set_rank_export")
-        rc = L.ns_decode_step(self.ctx._h, _ptr(logits), logits.stride(0), self.B, _ptr(tok), _ptr(last), _ptr(act),
-                              _ptr(self.state), _ptr(self.out_bits), self.out_stride, float(p.temp), int(p.topk),
-                              self.ctx._banned, self.ctx._nbanned, ctypes.c_void_p(0), 0, _stream_handle())
+        with _table_registered(self.ctx, self.qtable, self.k_max):
+            rc = L.ns_decode_step(self.ctx._h, _ptr(logits), logits.stride(0), self.B, _ptr(tok), _ptr(last), _ptr(act),
+                                  _ptr(self.state), _ptr(self.out_bits), self.out_stride, float(p.temp), int(p.topk),
+                                  self.ctx._banned, self.ctx._nbanned, ctypes.c_void_p(0), 0, _stream_handle())
         L.ns_set_rank_export(self.ctx._h, ctypes.c_void_p(0), 0)
         self.ctx.check(rc, "ns_decode_step")
 

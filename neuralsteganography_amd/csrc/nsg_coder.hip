@@ -768,6 +768,7 @@ __global__ __launch_bounds__((NSPLIT > 1 ? NSPLIT : WPB) * WAVE, NSG_MIN_WAVES_P
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
     const int b = __builtin_amdgcn_readfirstlane(NSPLIT > 1 ? (int)blockIdx.x : (int)blockIdx.x * WPB + wv);
     if (b >= p.B) return;
+    const RowQuality sq = row_quality(p, b);  // this stream's table row, or the call's scalars
 
     NSG_STAMP_RT(p, b, lane, 9);
     NSG_STAMP(p, b, lane, 0);
@@ -785,11 +786,11 @@ __global__ __launch_bounds__((NSPLIT > 1 ? NSPLIT : WPB) * WAVE, NSG_MIN_WAVES_P
     }
 
     const int V = p.V;
-    const int K = p.K;
+    const int K = sq.K;
     const char* rowc = (const char*)p.logits + (int64_t)b * p.ld * (int64_t)sizeof(T);
     const RowReader rd(rowc, (uint32_t)(p.ld * (int64_t)sizeof(T)));
     const int ntiles = (V + TS - 1) / TS;
-    const float c32 = p.c32;
+    const float c32 = sq.c32;
 
     Cand cand;
     cand.keys = s_keys[wv];
@@ -803,7 +804,7 @@ __global__ __launch_bounds__((NSPLIT > 1 ? NSPLIT : WPB) * WAVE, NSG_MIN_WAVES_P
     int nfallback = 0;
 
     // ---------------- stream order ----------------
-    // With a sample (p.spec_j > 0) NSAMP whole tiles spread over the row -- tile s*space + space-1, 4,096 ids --
+    // With a sample (spec_j > 0) NSAMP whole tiles spread over the row -- tile s*space + space-1, 4,096 ids --
     // are read first and give r and the speculative threshold.  The last NKEEP of them stay in registers and
     // are accumulated and offered like any other tile; the stream visits every other tile in increasing order,
     // the first NSAMP - NKEEP sample tiles included (fp32 rows: keeping all 16 would spill; those 8 KiB are read
@@ -814,7 +815,7 @@ __global__ __launch_bounds__((NSPLIT > 1 ? NSPLIT : WPB) * WAVE, NSG_MIN_WAVES_P
     constexpr int S0 = NSAMP - NKEEP;  // first kept sample tile
     static_assert(NKEEP >= PREFETCH && NKEEP % PREFETCH == 0, "kept sample tiles come in ring-sized groups");
     static_assert(NSPLIT == 1 || NSPLIT == NSAMP, "split: one wave per sample tile");
-    const bool spec_on = p.spec_j > 0;  // always on in the split form (host)
+    const bool spec_on = sq.spec_j > 0;  // always on in the split form (host); with a table, for every row or none
     const int space = spec_on ? ntiles / NSAMP : 1;
     // split: wave w streams tiles [w*space, end) minus its sample tile w*space + space-1; the last wave takes the rest
     const int nstream = !spec_on ? ntiles
@@ -892,7 +893,7 @@ __global__ __launch_bounds__((NSPLIT > 1 ? NSPLIT : WPB) * WAVE, NSG_MIN_WAVES_P
         for (int bit = 31; bit >= 16; --bit) {
             const uint32_t c = pre | (1u << bit);
             const int n = popc64(ballot(u0 >= c)) + popc64(ballot(u1 >= c)) + popc64(ballot(u2 >= c));
-            if (n >= p.spec_j) pre = c;
+            if (n >= sq.spec_j) pre = c;
         }
         if (pre > 0x00800000u) {
             set_thr(cand, unord32(pre - 1u));
@@ -930,7 +931,7 @@ __global__ __launch_bounds__((NSPLIT > 1 ? NSPLIT : WPB) * WAVE, NSG_MIN_WAVES_P
         for (int bit = 31; bit >= 16; --bit) {
             const uint32_t c = pre | (1u << bit);
             const int n = popc64(ballot(o0 >= c)) + popc64(ballot(o1 >= c)) + popc64(ballot(o2 >= c));
-            if (n >= p.spec_j) pre = c;
+            if (n >= sq.spec_j) pre = c;
         }
         if (pre > 0x00800000u) {  // above ord(-inf): a finite threshold
             set_thr(cand, unord32(pre - 1u));  // x > thr  <=>  ord(x) >= pre
@@ -945,7 +946,7 @@ __global__ __launch_bounds__((NSPLIT > 1 ? NSPLIT : WPB) * WAVE, NSG_MIN_WAVES_P
     double b64 = 0.0, u64 = 0.0;  // STATS: sum e (x-r), sum exp(x-r) untempered
     int bi = 0;
     int next_ban = p.nbanned > 0 ? p.banned[0] : 0x7FFFFFFF;
-    if (p.spec_j <= 0) {  // no sample (small vocab): reference = max of the first tile
+    if (sq.spec_j <= 0) {  // no sample (small vocab): reference = max of the first tile
         float x[W];
         Elem<T>::unpack(buf[0], x);
         int bi0 = 0, nb0 = next_ban;
@@ -1279,7 +1280,7 @@ __global__ __launch_bounds__((NSPLIT > 1 ? NSPLIT : WPB) * WAVE, NSG_MIN_WAVES_P
 #pragma unroll
     for (int s = 0; s < NSK; ++s) {
         const int i = s * WAVE + lane;
-        e[s] = (s < nsk && i < K) ? exp_canon(((double)key_val(sk[s]) - m) * p.inv_temp) : 0.0;
+        e[s] = (s < nsk && i < K) ? exp_canon(((double)key_val(sk[s]) - m) * sq.inv_temp) : 0.0;
     }
     const double S_r = wave_sum_butterfly(acc64);
     // row statistics (STATS builds; tolerance-checked, not part of the bit contract)
@@ -1288,7 +1289,8 @@ __global__ __launch_bounds__((NSPLIT > 1 ? NSPLIT : WPB) * WAVE, NSG_MIN_WAVES_P
     if (want_stats) {
         const double B_r = wave_sum_butterfly(b64);
         const double U_r = wave_sum_butterfly(u64);
-        if (!row_stats_from_stream(S_r, B_r, U_r, r, m, p.inv_temp, rs)) rs = wave_row_stats<T>(p, rowc, m, lane);
+        if (!row_stats_from_stream(S_r, B_r, U_r, r, m, sq.inv_temp, rs))
+            rs = wave_row_stats<T>(p, rowc, m, lane, sq.inv_temp);
     }
     if (!DECODE && p.sample) {
         sample_tail<NSK>(p, b, st, sk, e, nsk, K, m, rs, lane, want_stats);
@@ -1305,7 +1307,7 @@ __global__ __launch_bounds__((NSPLIT > 1 ? NSPLIT : WPB) * WAVE, NSG_MIN_WAVES_P
     double S_used = 0.0;
     int k0 = K;
     if (!exact) {
-        const double f = exp_canon(((double)r - m) * p.inv_temp);
+        const double f = exp_canon(((double)r - m) * sq.inv_temp);
         const double Sf = S_r * f;
         const double u24 = 5.9604644775390625e-08;  // 2^-24
         const double eb = 9.5367431640625e-07         // v_exp_f32 error (2^-20, generous)
@@ -1339,7 +1341,7 @@ __global__ __launch_bounds__((NSPLIT > 1 ? NSPLIT : WPB) * WAVE, NSG_MIN_WAVES_P
         }
     }
     if (exact) {
-        const double S = exact_row_sum<T>(p, rowc, m, lane);
+        const double S = exact_row_sum<T>(p, rowc, m, lane, sq.inv_temp);
         S_used = S;
         k0 = K;
 #pragma unroll
@@ -1352,7 +1354,7 @@ __global__ __launch_bounds__((NSPLIT > 1 ? NSPLIT : WPB) * WAVE, NSG_MIN_WAVES_P
         }
     }
     int k = k0 < 2 ? 2 : k0;
-    if (k > p.topk) k = p.topk;
+    if (k > sq.topk) k = sq.topk;
 
     // E = sum_{i<k} e_i, order-free (exact limb sums, canonical step 6)
     Mass ms{0.0, 0.0, 0.0, 0.0};
@@ -1398,12 +1400,12 @@ __global__ __launch_bounds__((NSPLIT > 1 ? NSPLIT : WPB) * WAVE, NSG_MIN_WAVES_P
     if (!DECODE) {
         const int64_t bp = st.bit_pos + lane;
         uint32_t bit = 0;
-        if (lane < p.P && bp < nbits) {
+        if (lane < sq.P && bp < nbits) {
             const uint8_t* pl = p.payload + (int64_t)b * p.payload_stride;
             bit = (pl[bp >> 3] >> (bp & 7)) & 1u;
         }
         const uint64_t mbits = ballot(bit != 0u);
-        const uint64_t idx = __builtin_bitreverse64(mbits) >> (64 - p.P);
+        const uint64_t idx = __builtin_bitreverse64(mbits) >> (64 - sq.P);
 #pragma unroll
         for (int s = 0; s < NSK; ++s) {
             if (s < nsk) {
@@ -1481,7 +1483,7 @@ __global__ __launch_bounds__((NSPLIT > 1 ? NSPLIT : WPB) * WAVE, NSG_MIN_WAVES_P
     NSG_STAMP(p, b, lane, 7);
     // state update: cross-lane values are gathered by shuffles, every lane computes the same scalars
     if (err == 0u) {
-        const int P = p.P;
+        const int P = sq.P;
         const uint64_t mask = (P >= 64) ? ~0ull : ((1ull << P) - 1ull);
         const uint64_t new_lo = sel > 0 ? (uint64_t)(cum_at(sel - 1) + shift) : st.lo;
         const uint64_t new_hi = (uint64_t)(cum_at(sel) + shift);
@@ -1604,12 +1606,12 @@ __global__ __launch_bounds__(WPB* WAVE) void finish_sent_kernel(StepParams p, co
     }
 }
 
-__global__ void init_state_kernel(ns_stream_state* st, int B, int P) {
+__global__ void init_state_kernel(ns_stream_state* st, int B, int P, const ns_stream_quality* quality) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b < B) {
         ns_stream_state s;
         s.lo = 0;
-        s.hi = 1ull << P;
+        s.hi = 1ull << (quality ? quality[b].precision : P);
         s.bit_pos = 0;
         s.ntokens = 0;
         s.flags = 0;
@@ -1701,7 +1703,7 @@ static bool launch(ns_ctx* ctx, const nsg::StepParams& p, hipStream_t s) {
 
 extern "C" {
 
-const char* ns_version(void) { return "nsgcoder 0.30 gfx950"; }
+const char* ns_version(void) { return "nsgcoder 0.31 gfx950"; }
 
 int ns_set_split_max_batch(int max_batch) {
     const int prev = split_setting();
@@ -1749,6 +1751,8 @@ ns_ctx* ns_create(int device, int max_batch, int vocab, int max_k, int precision
     ctx->rk_idmap = nullptr;
     ctx->rk_idmap_stride = 0;
     ctx->rk_dict = 0;
+    ctx->quality = nullptr;
+    ctx->q_kmax = 0;
     const size_t cbytes = 4 * NS_COUNTER_SHARDS * sizeof(unsigned long long);
     if (hipMalloc((void**)&ctx->d_counters, cbytes) != hipSuccess || hipMemset(ctx->d_counters, 0, cbytes) != hipSuccess) {
         fail(nullptr, NS_ERR_HIP, "ns_create: hipMalloc failed");
@@ -1776,9 +1780,48 @@ int ns_init_state(ns_ctx* ctx, ns_stream_state* d_state, int B, void* hip_stream
     if (!ctx || !d_state || B < 1 || B > ctx->max_batch) return fail(ctx, NS_ERR_CONFIG, "ns_init_state: bad argument");
     const int threads = 256;
     hipLaunchKernelGGL(nsg::init_state_kernel, dim3((B + threads - 1) / threads), dim3(threads), 0,
-                       (hipStream_t)hip_stream, d_state, B, ctx->precision);
+                       (hipStream_t)hip_stream, d_state, B, ctx->precision, ctx->quality);
     if (hipGetLastError() != hipSuccess) return fail(ctx, NS_ERR_HIP, "ns_init_state: launch failed");
     return NS_OK;
+}
+
+// Banned ids inside [0, vocab), sorted and unique; returns their count.
+static int clean_banned(int vocab, const int32_t* banned, int nbanned, int* ban) {
+    int nb = 0;
+    for (int i = 0; i < nbanned; ++i)
+        if (banned[i] >= 0 && banned[i] < vocab) ban[nb++] = banned[i];
+    std::sort(ban, ban + nb);
+    return (int)(std::unique(ban, ban + nb) - ban);
+}
+
+// Speculative candidate threshold: the spec_j-th largest of a 64*NSG_SAMPLE-id stratified sample (whole tiles
+// spread over the row; the kernel needs at least two sample spacings, hence vocab >= 2 * 64*NSG_SAMPLE).  The
+// number of sample ids above the row's true K-th key is ~Poisson(lambda = 64*NSG_SAMPLE*K / nvalid); spec_j is
+// the smallest j with P(Poisson(lambda) >= j) <= 1e-6, so a miss (one extra row read by that wave) stays a rare
+// event for every K.  The kernel counts each lane's three largest sample values, so spec_j stays well below
+// 3*64.  NSG_SPEC_FACTOR (tuning override) instead sets spec_j = factor * lambda + 1.  0: no sample.  The result
+// does not decrease with K, so a sample that is on at some K is on at every smaller one.
+static int spec_j_rule(int vocab, int nvalid, int K) {
+    static const double spec_factor = [] {
+        const char* e = getenv("NSG_SPEC_FACTOR");
+        return e ? atof(e) : 0.0;
+    }();
+    if (vocab < 2 * 64 * NSG_SAMPLE) return 0;
+    const double lambda = (double)K * (64.0 * NSG_SAMPLE) / (double)nvalid;
+    int sj;
+    if (spec_factor > 0.0) {
+        sj = (int)(spec_factor * lambda) + 1;
+    } else {
+        double term = exp(-lambda), tail = 1.0;  // tail = P(X >= j), term = P(X = j)
+        sj = 0;
+        while (tail > 1e-6 && sj < 1024) {
+            tail -= term;
+            ++sj;
+            term *= lambda / (double)sj;
+        }
+    }
+    if (sj < 4) sj = 4;
+    return sj <= 160 ? sj : 0;
 }
 
 static int prepare(ns_ctx* ctx, nsg::StepParams& p, const void* d_logits, int64_t ld, int B, double temp,
@@ -1790,16 +1833,16 @@ static int prepare(ns_ctx* ctx, nsg::StepParams& p, const void* d_logits, int64_
     if (!d_logits || !d_state || B < 1 || B > ctx->max_batch) return fail(ctx, NS_ERR_CONFIG, "bad batch or pointer");
     if (ld < ctx->vocab || (ld % W) != 0) return fail(ctx, NS_ERR_CONFIG, "ld must be >= vocab and a multiple of 16 bytes");
     if (((uintptr_t)d_logits & 15u) != 0u) return fail(ctx, NS_ERR_CONFIG, "logits must be 16-byte aligned");
+    if (ctx->quality) {  // per-stream rows: the call's temp / topk are ignored, the host decides from k_max alone
+        temp = 1.0;
+        topk = ctx->q_kmax;
+    }
     if (!(temp > 0.0)) return fail(ctx, NS_ERR_CONFIG, "temperature must be positive");
     if (topk < 1) return fail(ctx, NS_ERR_CONFIG, "topk must be positive");
     if (nbanned < 0 || nbanned > NS_MAX_BANNED || (nbanned > 0 && !banned))
         return fail(ctx, NS_ERR_CONFIG, "too many banned ids");
     int ban[NS_MAX_BANNED];
-    int nb = 0;
-    for (int i = 0; i < nbanned; ++i)
-        if (banned[i] >= 0 && banned[i] < ctx->vocab) ban[nb++] = banned[i];
-    std::sort(ban, ban + nb);
-    nb = (int)(std::unique(ban, ban + nb) - ban);
+    const int nb = clean_banned(ctx->vocab, banned, nbanned, ban);
     const int nvalid = ctx->vocab - nb;
     if (nvalid < 2) return fail(ctx, NS_ERR_CONFIG, "fewer than two valid token ids");
     const int K = std::min(topk, nvalid);
@@ -1819,34 +1862,8 @@ static int prepare(ns_ctx* ctx, nsg::StepParams& p, const void* d_logits, int64_
     p.nbanned = nb;
     for (int i = 0; i < nb; ++i) p.banned[i] = ban[i];
     p.flags = flags;
-    // speculative candidate threshold: the spec_j-th largest of a 64*NSG_SAMPLE-id stratified sample (whole tiles
-    // spread over the row; the kernel needs at least two sample spacings, hence vocab >= 2 * 64*NSG_SAMPLE).  The
-    // number of sample ids above the row's true K-th key is ~Poisson(lambda = 64*NSG_SAMPLE*K / nvalid); spec_j is
-    // the smallest j with P(Poisson(lambda) >= j) <= 1e-6, so a miss (one extra row read by that wave) stays a rare
-    // event for every K.  The kernel counts each lane's three largest sample values, so spec_j stays well below
-    // 3*64.  NSG_SPEC_FACTOR (tuning override) instead sets spec_j = factor * lambda + 1.
-    p.spec_j = 0;
-    static const double spec_factor = [] {
-        const char* e = getenv("NSG_SPEC_FACTOR");
-        return e ? atof(e) : 0.0;
-    }();
-    if (ctx->vocab >= 2 * 64 * NSG_SAMPLE) {
-        const double lambda = (double)K * (64.0 * NSG_SAMPLE) / (double)nvalid;
-        int sj;
-        if (spec_factor > 0.0) {
-            sj = (int)(spec_factor * lambda) + 1;
-        } else {
-            double term = exp(-lambda), tail = 1.0;  // tail = P(X >= j), term = P(X = j)
-            sj = 0;
-            while (tail > 1e-6 && sj < 1024) {
-                tail -= term;
-                ++sj;
-                term *= lambda / (double)sj;
-            }
-        }
-        if (sj < 4) sj = 4;
-        if (sj <= 160) p.spec_j = sj;
-    }
+    p.spec_j = spec_j_rule(ctx->vocab, nvalid, K);
+    p.quality = ctx->quality;
     p.state = d_state;
     p.trace = d_trace;
     p.counters = ctx->d_counters;
@@ -1919,6 +1936,7 @@ int ns_sample_step(ns_ctx* ctx, const void* d_logits, int64_t ld, int B, uint64_
     if (ctx && ctx->dtype == NS_DTYPE_F64)
         return fail(ctx, NS_ERR_CONFIG, "ns_sample_step: a NS_DTYPE_F64 context holds provider probability rows (rank coder only)");
     if (!ctx) return fail(ctx, NS_ERR_CONFIG, "null context");
+    if (ctx->quality) return fail(ctx, NS_ERR_CONFIG, "ns_sample_step: a stream quality table is registered");
     nsg::StepParams p;
     const int tk = topk > 0 ? topk : ctx->vocab;  // sample.py: topk <= 0 keeps every id
     int rc = prepare(ctx, p, d_logits, ld, B, temp, tk, banned, nbanned, d_trace, step_flags, d_state);
@@ -1940,6 +1958,7 @@ int ns_sample_step(ns_ctx* ctx, const void* d_logits, int64_t ld, int B, uint64_
 static int rank_prepare(ns_ctx* ctx, nsg::StepParams& p, const void* d_logits, int64_t ld, int B, double temp,
                         const ns_rank_quality* q, ns_step_trace* d_trace, uint32_t flags, ns_stream_state* d_state) {
     if (!ctx) return fail(ctx, NS_ERR_CONFIG, "null context");
+    if (ctx->quality) return fail(ctx, NS_ERR_CONFIG, "rank step: a stream quality table is registered");
     if (!q) return fail(ctx, NS_ERR_CONFIG, "rank step: null quality");
     if (q->top_p > 1.0) return fail(ctx, NS_ERR_CONFIG, "top_p must be within (0, 1]");
     if (q->prob_temp > 0.0 && (q->cap_bits > 0 || q->min_prob >= 0.0))
@@ -2023,7 +2042,7 @@ int ns_token_probs(ns_ctx* ctx, const void* d_logits, int64_t ld, int B, double 
     p.probs_out = d_probs;
     p.probs_stride = probs_stride;
     hipLaunchKernelGGL(nsg::init_state_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)hip_stream,
-                       d_scratch_state, B, ctx->precision);
+                       d_scratch_state, B, ctx->precision, (const ns_stream_quality*)nullptr);
     if (!nsg_rank_launch(ctx, p, true, (hipStream_t)hip_stream))
         return fail(ctx, NS_ERR_HIP, "ns_token_probs: launch failed");
     return NS_OK;
@@ -2059,6 +2078,51 @@ int ns_set_stamps(ns_ctx* ctx, uint64_t* d_stamps) {  // diagnostic builds only 
 int ns_set_stats(ns_ctx* ctx, double* d_stats) {
     if (!ctx) return fail(ctx, NS_ERR_CONFIG, "null context");
     ctx->stats = d_stats;
+    return NS_OK;
+}
+
+int ns_stream_quality_fill(int vocab, const int32_t* banned, int nbanned, double temp, int topk, int precision,
+                           int k_max, ns_stream_quality* out_row) {
+    if (!out_row || vocab < 2) return fail(nullptr, NS_ERR_CONFIG, "ns_stream_quality_fill: bad argument");
+    if (nbanned < 0 || nbanned > NS_MAX_BANNED || (nbanned > 0 && !banned))
+        return fail(nullptr, NS_ERR_CONFIG, "ns_stream_quality_fill: too many banned ids");
+    if (!(temp > 0.0)) return fail(nullptr, NS_ERR_CONFIG, "ns_stream_quality_fill: temperature must be positive");
+    if (topk < 1 || topk > k_max) return fail(nullptr, NS_ERR_CONFIG, "ns_stream_quality_fill: topk outside [1, k_max]");
+    if (precision < 1 || precision > 60)
+        return fail(nullptr, NS_ERR_CONFIG, "ns_stream_quality_fill: precision outside [1, 60]");
+    int ban[NS_MAX_BANNED];
+    const int nvalid = vocab - clean_banned(vocab, banned, nbanned, ban);
+    if (nvalid < 2) return fail(nullptr, NS_ERR_CONFIG, "ns_stream_quality_fill: fewer than two valid token ids");
+    ns_stream_quality row;
+    row.inv_temp = 1.0 / temp;
+    row.c32 = (float)(row.inv_temp * 1.4426950408889634);
+    row.topk = topk;
+    row.K = std::min(topk, nvalid);
+    row.precision = precision;
+    // the sample is on for every row of a call or for none: off at k_max switches it off here
+    row.spec_j = spec_j_rule(vocab, nvalid, std::min(k_max, nvalid)) > 0 ? spec_j_rule(vocab, nvalid, row.K) : 0;
+    row.reserved = 0;
+    *out_row = row;
+    return NS_OK;
+}
+
+int ns_set_stream_quality(ns_ctx* ctx, const ns_stream_quality* d_table, int k_max) {
+    if (!ctx) return fail(ctx, NS_ERR_CONFIG, "ns_set_stream_quality: null context");
+    if (!d_table) {
+        ctx->quality = nullptr;
+        ctx->q_kmax = 0;
+        return NS_OK;
+    }
+    if (ctx->dtype == NS_DTYPE_F64)
+        return fail(ctx, NS_ERR_CONFIG, "ns_set_stream_quality: a NS_DTYPE_F64 context runs the rank coder only");
+    if (k_max < 1 || ((uintptr_t)d_table & 7u) != 0u)
+        return fail(ctx, NS_ERR_CONFIG, "ns_set_stream_quality: k_max must be positive and the table 8-byte aligned");
+    if (k_max > ns_max_topk(ctx->dtype))
+        return fail(ctx, NS_ERR_UNSUPPORTED,
+                    "ns_set_stream_quality: k_max beyond the single-pass limit (ns_max_topk): the wide path takes "
+                    "one quality per call");
+    ctx->quality = d_table;
+    ctx->q_kmax = k_max;
     return NS_OK;
 }
 

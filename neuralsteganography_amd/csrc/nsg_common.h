@@ -316,7 +316,35 @@ struct StepParams {
     ns_stream_state* state;
     ns_step_trace* trace;
     unsigned long long* counters;
+    // per-stream quality rows (ns_set_stream_quality), nullable: then P, topk, K, inv_temp, c32 and spec_j above
+    // hold for every stream.  With a table, K and spec_j above are those of the call's k_max (host decisions).
+    const ns_stream_quality* quality;
 };
+
+// The quality of stream b (wave-uniform): its table row, or the call's scalars.  b is wave-uniform, so the row is
+// read once at entry and every field is pinned to scalar registers.  K is clamped to the call's k_max (p.K), the
+// bound the launch sized the rank slots for.
+struct RowQuality {
+    double inv_temp;
+    float c32;
+    int P, topk, K, spec_j;
+};
+__device__ __forceinline__ RowQuality row_quality(const StepParams& p, int b) {
+    RowQuality q{p.inv_temp, p.c32, p.P, p.topk, p.K, p.spec_j};
+    if (p.quality) {
+        const ns_stream_quality row = p.quality[b];
+        const uint64_t it = __builtin_bit_cast(uint64_t, row.inv_temp);
+        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)it);
+        const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(it >> 32));
+        q.inv_temp = __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+        q.c32 = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(row.c32)));
+        q.P = __builtin_amdgcn_readfirstlane(row.precision);
+        q.topk = __builtin_amdgcn_readfirstlane(row.topk);
+        q.K = min(max(__builtin_amdgcn_readfirstlane(row.K), 1), p.K);
+        q.spec_j = __builtin_amdgcn_readfirstlane(row.spec_j);
+    }
+    return q;
+}
 
 // In-kernel phase stamps (diagnostic builds only: -DNSG_STAMPS=1, tools/stamp_phases.py)
 #ifdef NSG_STAMPS
@@ -386,7 +414,8 @@ __device__ __forceinline__ bool is_banned(const StepParams& p, int j) {
 
 // exact canonical row sum (oracle or_row_sum): id j -> lane (j>>2)&63, per-lane increasing, butterfly
 template <typename T>
-__device__ __forceinline__ double exact_row_sum(const StepParams& p, const void* row, double m, int lane) {
+__device__ __forceinline__ double exact_row_sum(const StepParams& p, const void* row, double m, int lane,
+                                                double inv_temp) {
     double acc = 0.0;
     const int ngroups = (p.V + 3) >> 2;
     for (int g = lane; g < ngroups; g += WAVE) {
@@ -395,26 +424,31 @@ __device__ __forceinline__ double exact_row_sum(const StepParams& p, const void*
             const int j = 4 * g + q;
             if (j < p.V && !is_banned(p, j)) {
                 const float x = Elem<T>::load1(row, j) + 0.0f;
-                acc += exp_canon(((double)x - m) * p.inv_temp);
+                acc += exp_canon(((double)x - m) * inv_temp);
             }
         }
     }
     return wave_sum_butterfly(acc);
+}
+template <typename T>
+__device__ __forceinline__ double exact_row_sum(const StepParams& p, const void* row, double m, int lane) {
+    return exact_row_sum<T>(p, row, m, lane, p.inv_temp);
 }
 
 // Statistics fallback (streaming accumulators unusable): re-read the row, float64 exps against the true max.
 // Inlined (round 5): as a call it made the statistics builds of the coder keep a stack frame and spill around it
 // -- 4.9 KB of scratch per lane in the fp16 one-wave form, 1.10 ms per step at B = 4,096 against 0.19 inlined.
 template <typename T>
-__device__ __forceinline__ RowStats wave_row_stats(const StepParams& p, const void* row, double m, int lane) {
+__device__ __forceinline__ RowStats wave_row_stats(const StepParams& p, const void* row, double m, int lane,
+                                                   double inv_temp) {
     double s1 = 0.0, st = 0.0, at = 0.0;
     for (int j = lane; j < p.V; j += WAVE) {
         if (is_banned(p, j)) continue;
         const double d = (double)(Elem<T>::load1(row, j) + 0.0f) - m;
-        const double et = exp(d * p.inv_temp);
+        const double et = exp(d * inv_temp);
         s1 += exp(d);
         st += et;
-        at += et * (d * p.inv_temp);
+        at += et * (d * inv_temp);
     }
     s1 = wave_sum_butterfly(s1);
     st = wave_sum_butterfly(st);
@@ -424,6 +458,10 @@ __device__ __forceinline__ RowStats wave_row_stats(const StepParams& p, const vo
     rs.lst = log(st);
     rs.a_over_s = at / st;
     return rs;
+}
+template <typename T>
+__device__ __forceinline__ RowStats wave_row_stats(const StepParams& p, const void* row, double m, int lane) {
+    return wave_row_stats<T>(p, row, m, lane, p.inv_temp);
 }
 
 __device__ __forceinline__ const void* uniform_ptr(const void* ptr) {

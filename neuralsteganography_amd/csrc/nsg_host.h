@@ -60,6 +60,8 @@ struct ns_ctx {
     const int32_t* rk_count;  // NS_DTYPE_F64: entries per row [B] (ns_set_rank_rows), nullable = vocab
     const int32_t* rk_idmap;  // NS_DTYPE_F64: token id of each row entry [B][idmap_stride], nullable = position
     int64_t rk_idmap_stride;
+    const ns_stream_quality* quality;  // per-stream quality rows (ns_set_stream_quality), nullable
+    int q_kmax;               // the table's k_max: every host decision of a step with a table
     int rk_dict;              // NS_DTYPE_F64: rows are dict ProbDists (cap_bits universe, codec/quality.py:161-171)
     std::string err;
 };

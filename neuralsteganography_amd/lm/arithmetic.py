@@ -17,7 +17,8 @@ from __future__ import annotations
 from collections import deque
 from typing import Deque, Dict, Iterable, List, Mapping, Optional, Sequence
 
-from ..coder import CoderContext, CoderParams, DecodeSession, EncodeSession, SampleSession, StreamingDecodeSession
+from ..coder import (CoderContext, CoderParams, DecodeSession, EncodeSession, SampleSession, StreamQuality,
+                     StreamingDecodeSession)
 from ..exceptions import ConfigurationError
 
 CodecState = Dict[str, object]
@@ -181,15 +182,18 @@ class HipArithmeticLM:
         self._decode_states: Deque[CodecState] = deque()
 
     # ---------------------------------------------------------------- plumbing
-    def _coder(self, params: CoderParams, B: int) -> CoderContext:
+    def _coder(self, params: CoderParams, B: int, mixed: bool = False) -> CoderContext:
         """Coder context for ``params`` serving batches up to ``B``.  Keyed on the parameters only (the kernels
         take B per call): a context built for a larger batch serves every smaller one, a larger B replaces it,
         and at most ``CTX_CACHE_SIZE`` parameter sets stay alive (least recently used closed first) -- each
-        wide-path context holds 2*B*V*8 bytes of sort keys."""
+        wide-path context holds 2*B*V*8 bytes of sort keys.  ``mixed``: the context of a call with per-message
+        qualities (``params.topk`` is its ``k_max``), whose steps read temperature and precision from the table."""
         key = (params.vocab, params.precision, params.temp, params.topk, params.dtype,
                tuple(params.banned_ids()))
+        if mixed:
+            key = (params.vocab, params.dtype, tuple(params.banned_ids()), params.topk, "mixed")
         ctx = self._ctx_cache.pop(key, None)
-        if ctx is not None and ctx.max_batch < B:
+        if ctx is not None and (ctx.max_batch < B or ctx.params.precision < params.precision):
             ctx.close()
             ctx = None
         if ctx is None:
@@ -244,7 +248,7 @@ class HipArithmeticLM:
         return [int(t) for t in bos + body]
 
     def encode_arithmetic(self, bits: List[int], context: List[int], *, quality: Mapping[str, object]) -> List[int]:
-        toks = self.encode_batch([bits], context, quality=quality)[0]
+        toks = self.encode_batch([bits], context, quality=quality if quality is not None else {})[0]
         return toks
 
     def decode_arithmetic(self, tokens: List[int], context: List[int], *, quality: Mapping[str, object]) -> List[int]:
@@ -254,7 +258,7 @@ class HipArithmeticLM:
         nbits = None
         if state is not None and state.get("residual_bits"):
             nbits = int.from_bytes(bytes(state["residual_bits"]), byteorder="big", signed=False)
-        out = self.decode_batch([tokens], context, quality=quality)[0]
+        out = self.decode_batch([tokens], context, quality=quality if quality is not None else {})[0]
         return out[:nbits] if nbits is not None else out
 
     def drain_states(self) -> List[CodecState]:
@@ -268,7 +272,8 @@ class HipArithmeticLM:
     # ---------------------------------------------------------------- batched entry points
     def encode_batch(self, bit_lists: Sequence[Sequence[int]], context: Optional[Sequence[int]] = None, *,
                      contexts: Optional[Sequence[Sequence[int]]] = None,
-                     quality: Mapping[str, object], check_every: int = 16,
+                     quality: Optional[Mapping[str, object]] = None,
+                     qualities: Optional[Sequence[Mapping[str, object]]] = None, check_every: int = 16,
                      stall_steps: int = 4096, return_stats: bool = False, stop_text: Optional[str] = None,
                      graphs: Optional[bool] = None, slots: Optional[int] = None):
         """Encode independent bit lists (one GPT-2 forward + one coder launch per token for every live stream).
@@ -288,6 +293,15 @@ class HipArithmeticLM:
         All-equal ``contexts`` take the shared-context path; non-native LMs run their lockstep loop once per distinct
         context.
 
+        Exactly one of ``quality`` (shared) and ``qualities`` (one per message: its own temperature, top-k and
+        precision, as each ``stego_encode`` call of the reference has its own ``quality``) is given.  The coder step
+        then reads every stream's values from its row of a device table (``ns_set_stream_quality``), so the messages
+        still run as ONE batch; message ``m``'s tokens equal ``encode_batch([bits], ..., quality=qualities[m])[0]``.
+        ``finish_sent`` is a flag of the whole step and must agree across the call.  All-equal ``qualities`` take the
+        ``quality`` path.  Messages whose top-k exceeds the single-pass limit (``ns_max_topk``: the wide path takes
+        one quality per call) run as one more call per distinct such quality, results back in the caller's order
+        (``last_schedule["quality_groups"]``).
+
         With ``graphs`` (default) the native model's per-token step is captured once as a hipGraph and replayed,
         which removes the per-launch host cost (it dominates at small batch, and at B = 4096 it keeps the GPU busy
         across the host checks).  Non-native models ignore ``graphs``: their lockstep loop runs eagerly, and its token
@@ -299,23 +313,28 @@ class HipArithmeticLM:
         :class:`ArithmeticRangeError` instead of hanging."""
         B = len(bit_lists)
         context, contexts = _one_or_many(context, contexts, B)
+        quality, plist = self._quality_or_many(quality, qualities, B)
         if B == 0:
             return []
+        kw = dict(check_every=check_every, stall_steps=stall_steps, return_stats=return_stats, stop_text=stop_text,
+                  graphs=graphs, slots=slots)
+        groups = _quality_groups(plist, self._single_pass_limit()) if plist is not None else None
+        if groups is not None and len(groups) > 1:
+            n_enc, n_dec = len(self._encode_states), len(self._decode_states)
+            res = self._by_group(self.encode_batch, bit_lists, groups, context, contexts, qualities, return_stats, **kw)
+            self._requeue_states(n_enc, n_dec, bit_lists)
+            self.last_schedule = dict(getattr(self, "last_schedule", None) or {}, quality_groups=len(groups))
+            return res
         if contexts is not None and not getattr(self.lm, "native", False):
             n_enc, n_dec = len(self._encode_states), len(self._decode_states)
-            res = self._by_context(self.encode_batch, bit_lists, contexts, return_stats,
-                                   quality=quality, check_every=check_every, stall_steps=stall_steps,
-                                   return_stats=return_stats, stop_text=stop_text, graphs=graphs, slots=slots)
-            del self._encode_states[n_enc:]  # the groups queued their bit counts group by group: the caller's order
-            while len(self._decode_states) > n_dec:
-                self._decode_states.pop()
-            for b in bit_lists:
-                sc = _bits_count_state(len(b))
-                self._encode_states.append(sc)
-                self._decode_states.append(dict(sc))
+            res = self._by_context(self.encode_batch, bit_lists, contexts, return_stats, qualities=qualities,
+                                   quality=quality, **kw)
+            self._requeue_states(n_enc, n_dec, bit_lists)
             return res
-        params = coder_params_from_quality(quality, self.vocab, self.logits_dtype, self.banned)
-        finish = bool(dict(quality or {}).get("finish_sent", False))
+        sq = StreamQuality(plist) if plist is not None else None  # per-message rows: one mixed batch
+        params = sq.context_params() if sq is not None else \
+            coder_params_from_quality(quality, self.vocab, self.logits_dtype, self.banned)
+        finish = bool(dict((qualities[0] if sq is not None else quality) or {}).get("finish_sent", False))
         max_bits = max(len(b) for b in bit_lists)
         budget = 2 * max_bits + 64            # initial KV/history capacity (grows on demand)
         hard_cap = 64 * max_bits + 4096       # a stream fixing < 1/64 bit per token is reported, not looped
@@ -325,30 +344,30 @@ class HipArithmeticLM:
             from .slots import SlotEncoder
 
             S = max(1, min(B, int(slots) if slots else self.max_batch))
-            ctx = self._coder(params, S)
+            ctx = self._coder(params, S, mixed=sq is not None)
             if finish:
                 ctx.set_sentence_end(self.sentence_end_table())
             enc = SlotEncoder(self, ctx, bit_lists, context, slots=S, finish=finish, stop_text=stop_text,
                               stats=return_stats, check_every=check_every, stall_steps=stall_steps, hard_cap=hard_cap,
                               use_graph=bool(graphs), compact=self.slot_compaction, contexts=contexts,
-                              share=self.share_contexts)
+                              share=self.share_contexts, qualities=sq)
             toks, st = enc.run()
             self.last_schedule = {"slots": S, "evictions": enc.evictions, "compactions": enc.compactions,
                                   "max_live": enc.max_live, "kv_pages_peak": enc.kv_peak,
                                   "prefill_rows": enc.prefill_rows, "prefill_groups": enc.prefill_groups,
-                                  "prefill_shared": enc.prefill_shared}
+                                  "prefill_shared": enc.prefill_shared, "quality_groups": 1}
             for b in bit_lists:
                 sc = _bits_count_state(len(b))
                 self._encode_states.append(sc)
                 self._decode_states.append(dict(sc))
             return (toks, st) if return_stats else toks
-        ctx = self._coder(params, B)
+        ctx = self._coder(params, B, mixed=sq is not None)
         if finish:
             ctx.set_sentence_end(self.sentence_end_table())
         logits = self.lm.prefill(context, B, budget)
         # token history: starts at the KV budget and grows at the host checks (the 64x hard cap up front would be
         # 8.6 GB at B = 4096)
-        sess = EncodeSession(ctx, bit_lists, max_tokens=budget, stats=return_stats)
+        sess = EncodeSession(ctx, bit_lists, max_tokens=budget, stats=return_stats, quality=sq)
         stop = _StopCheck(self, sess, stop_text) if stop_text is not None else None
 
         def coder_step(lg):
@@ -402,41 +421,55 @@ class HipArithmeticLM:
 
     def decode_batch(self, token_lists: Sequence[Sequence[int]], context: Optional[Sequence[int]] = None, *,
                      contexts: Optional[Sequence[Sequence[int]]] = None,
-                     quality: Mapping[str, object], graphs: Optional[bool] = None,
+                     quality: Optional[Mapping[str, object]] = None,
+                     qualities: Optional[Sequence[Mapping[str, object]]] = None, graphs: Optional[bool] = None,
                      slots: Optional[int] = None) -> List[List[int]]:
         """Decode token lists (ragged); returns every emitted bit (callers truncate).  On the native GPU model the
         lists run through ``slots`` slots (:class:`~neuralsteganography_amd.lm.slots.SlotDecoder`, longest first,
         a message's pages mapped when it is admitted); with ``graphs`` the per-token step (coder + GPT-2 decode) is a
         replayed hipGraph, as in :meth:`encode_batch`.  Non-native models ignore ``graphs`` (eager lockstep loop).
-        ``context`` / ``contexts`` as in :meth:`encode_batch`: one shared context, or one per token list."""
+        ``context`` / ``contexts`` as in :meth:`encode_batch`: one shared context, or one per token list; ``quality``
+        / ``qualities`` likewise (one mixed batch, top-k beyond the single-pass limit grouped,
+        ``last_decode_schedule["quality_groups"]``)."""
         from ..codec.errors import DecodeDivergenceError
 
         B = len(token_lists)
         context, contexts = _one_or_many(context, contexts, B)
+        quality, plist = self._quality_or_many(quality, qualities, B)
         if B == 0:
             return []
+        groups = _quality_groups(plist, self._single_pass_limit()) if plist is not None else None
+        if groups is not None and len(groups) > 1:
+            res = self._by_group(self.decode_batch, token_lists, groups, context, contexts, qualities, False,
+                                 graphs=graphs, slots=slots)
+            self.last_decode_schedule = dict(getattr(self, "last_decode_schedule", None) or {},
+                                             quality_groups=len(groups))
+            return res
         if contexts is not None and not getattr(self.lm, "native", False):
-            return self._by_context(self.decode_batch, token_lists, contexts, False, quality=quality, graphs=graphs,
-                                    slots=slots)
+            return self._by_context(self.decode_batch, token_lists, contexts, False, qualities=qualities,
+                                    quality=quality, graphs=graphs, slots=slots)
         for tl in token_lists:  # received ids feed the embedding gather: validate on the host first
             if any((int(t) < 0 or int(t) >= self.vocab) for t in tl):
                 raise DecodeDivergenceError(f"received token id outside [0, {self.vocab})")
-        params = coder_params_from_quality(quality, self.vocab, self.logits_dtype, self.banned)
+        sq = StreamQuality(plist) if plist is not None else None  # per-message rows: one mixed batch
+        params = sq.context_params() if sq is not None else \
+            coder_params_from_quality(quality, self.vocab, self.logits_dtype, self.banned)
         if graphs is None:
             graphs = True
         if getattr(self.lm, "native", False):  # the product path: slots, pages mapped at admission (lm/slots.py)
             from .slots import SlotDecoder
 
             S = max(1, min(B, int(slots) if slots else self.max_batch))
-            dec = SlotDecoder(self, self._coder(params, S), token_lists, context, slots=S, use_graph=bool(graphs),
-                              compact=self.slot_compaction, contexts=contexts, share=self.share_contexts)
+            dec = SlotDecoder(self, self._coder(params, S, mixed=sq is not None), token_lists, context, slots=S,
+                              use_graph=bool(graphs), compact=self.slot_compaction, contexts=contexts,
+                              share=self.share_contexts, qualities=sq)
             out = dec.run()
             self.last_decode_schedule = {"slots": S, "evictions": dec.evictions, "compactions": dec.compactions,
                                          "prefill_rows": dec.prefill_rows, "prefill_groups": dec.prefill_groups,
-                                         "prefill_shared": dec.prefill_shared}
+                                         "prefill_shared": dec.prefill_shared, "quality_groups": 1}
             return out
-        ctx = self._coder(params, B)
-        sess = DecodeSession(ctx, token_lists)
+        ctx = self._coder(params, B, mixed=sq is not None)
+        sess = DecodeSession(ctx, token_lists, quality=sq)
         logits = self.lm.prefill(context, B, max(sess.T, 1) + 1)
         for t in range(sess.T):
             sess.step(logits)
@@ -444,22 +477,73 @@ class HipArithmeticLM:
                 logits = self.lm.step(sess.tok[t])
         return sess.bits()
 
-    def _by_context(self, entry, items, contexts, with_stats: bool, **kw):
+    def _by_context(self, entry, items, contexts, with_stats: bool, qualities=None, quality=None, **kw):
         """Non-native LMs: ``entry`` (``encode_batch`` / ``decode_batch``) once per distinct context over that
-        context's messages, results back in the caller's order."""
+        context's messages (each with its own quality when ``qualities`` is given), results back in the caller's
+        order."""
         groups: Dict[tuple, List[int]] = {}
         for i, c in enumerate(contexts):
             groups.setdefault(tuple(c), []).append(i)
         out: List[object] = [None] * len(items)
         stats: List[object] = [None] * len(items)
         for c, members in groups.items():
-            res = entry([items[i] for i in members], list(c), **kw)
+            qkw = {"quality": quality} if qualities is None else {"qualities": [qualities[i] for i in members]}
+            res = entry([items[i] for i in members], list(c), **qkw, **kw)
             res, st = res if with_stats else (res, None)
             for j, i in enumerate(members):
                 out[i] = res[j]
                 if st is not None:
                     stats[i] = st[j]
         return (out, stats) if with_stats else out
+
+    def _by_group(self, entry, items, groups, context, contexts, qualities, with_stats: bool, **kw):
+        """``entry`` once per quality group (:func:`_quality_groups`), each over its members with their own
+        contexts and qualities, results back in the caller's order."""
+        out: List[object] = [None] * len(items)
+        stats: List[object] = [None] * len(items)
+        for members in groups:
+            ckw = {"context": context} if contexts is None else {"contexts": [contexts[i] for i in members]}
+            res = entry([items[i] for i in members], **ckw, qualities=[qualities[i] for i in members], **kw)
+            res, st = res if with_stats else (res, None)
+            for j, i in enumerate(members):
+                out[i] = res[j]
+                if st is not None:
+                    stats[i] = st[j]
+        return (out, stats) if with_stats else out
+
+    def _requeue_states(self, n_enc: int, n_dec: int, bit_lists) -> None:
+        """After an encode that ran group by group (each group queued its bit counts): the states queued since
+        (``n_enc``, ``n_dec``) again, in the caller's order."""
+        del self._encode_states[n_enc:]
+        while len(self._decode_states) > n_dec:
+            self._decode_states.pop()
+        for b in bit_lists:
+            sc = _bits_count_state(len(b))
+            self._encode_states.append(sc)
+            self._decode_states.append(dict(sc))
+
+    def _single_pass_limit(self) -> int:
+        from .. import _lib
+
+        return _lib.max_topk(CoderParams(vocab=self.vocab, dtype=self.logits_dtype).dtype_code)
+
+    def _quality_or_many(self, quality, qualities, n: int):
+        """``(quality, None)`` for one shared quality, ``(None, params)`` -- one :class:`CoderParams` per message --
+        for ``qualities``; all-equal ``qualities`` are a shared quality.  Exactly one of the two must be given,
+        ``qualities`` one per message, and ``finish_sent`` (a flag of the whole step) must agree."""
+        if (quality is None) == (qualities is None):
+            raise ConfigurationError("give exactly one of quality (shared) and qualities (one per message)")
+        if qualities is None:
+            return quality, None
+        qs = [dict(q or {}) for q in qualities]
+        if len(qs) != n:
+            raise ConfigurationError(f"{len(qs)} qualities for {n} messages")
+        if len({bool(q.get("finish_sent", False)) for q in qs}) > 1:
+            raise ConfigurationError("finish_sent must agree across the qualities of one call")
+        plist = [coder_params_from_quality(q, self.vocab, self.logits_dtype, self.banned) for q in qs]
+        if all(p == plist[0] for p in plist):
+            return (qs[0] if qs else {}), None
+        return None, plist
 
     def decode_counted(self, token_lists: Sequence[Sequence[int]], context: Sequence[int], *,
                        quality: Mapping[str, object], done=None, check_every: int = 64):
@@ -619,6 +703,18 @@ class HipArithmeticLM:
             if t + 1 < length:
                 logits = self.lm.step(tok.to(torch.long))
         return sess.tokens(), (sess.stats() if stats else None)
+
+
+def _quality_groups(plist: Sequence[CoderParams], limit: int) -> List[List[int]]:
+    """Message indices per call of a ``qualities=`` request: every message whose top-k fits the single-pass kernel
+    (``limit`` = ``ns_max_topk``) in ONE mixed group, then one group per distinct (temp, topk, precision) beyond it
+    (the wide path takes one quality per call), in order of first appearance."""
+    mixed = [i for i, p in enumerate(plist) if p.topk <= limit]
+    wide: Dict[tuple, List[int]] = {}
+    for i, p in enumerate(plist):
+        if p.topk > limit:
+            wide.setdefault((p.temp, p.topk, p.precision), []).append(i)
+    return ([mixed] if mixed else []) + list(wide.values())
 
 
 def _one_or_many(context, contexts, n: int):

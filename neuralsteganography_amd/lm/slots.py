@@ -27,6 +27,11 @@ A stream's logits are bit-identical whatever the batch it runs in (the decode st
 paged attention), so a message's tokens are the same alone, in lockstep, or refilled into any slot.  Between host
 checks the step (coder + GPT-2 decode) is one captured hipGraph replay; a graph is re-captured when a buffer it
 holds is replaced (a wider page table, a longer history, a compaction).
+
+With ``qualities`` (one coder quality per message, library 0.31) every slot also has a row of the coder's stream
+quality table (``ns_set_stream_quality``): an admission -- the first fill, a refill, a re-admission after an eviction,
+with or without per-message contexts -- writes the message's row together with its payload and fresh state, a
+compaction permutes the table with the other per-slot tensors, and the table is part of the graph's layout key.
 """
 
 from __future__ import annotations
@@ -173,8 +178,9 @@ class SlotEncoder:
     def __init__(self, provider, ctx, bit_lists: Sequence[Sequence[int]], context: Sequence[int], *, slots: int,
                  finish: bool, stop_text: Optional[str], stats: bool, check_every: int, stall_steps: int,
                  hard_cap: int, use_graph: bool, compact: bool = True,
-                 contexts: Optional[Sequence[Sequence[int]]] = None, share: bool = True):
+                 contexts: Optional[Sequence[Sequence[int]]] = None, share: bool = True, qualities=None):
         self.p, self.lm, self.ctx = provider, provider.lm, ctx
+        self.qual = qualities  # coder.StreamQuality with one row per message, or None (the context's one quality)
         self.bits = bit_lists
         self.N = len(bit_lists)
         self.S = max(1, min(int(slots), self.N))
@@ -217,7 +223,8 @@ class SlotEncoder:
             first = lm.first_logits
         T0 = lm.kv.T0
         stride = max(1, (max_bits + 7) // 8)
-        sess = EncodeSession(self.ctx, self.bits[:S], max_tokens=budget, stats=self.stats, payload_stride=stride)
+        sess = EncodeSession(self.ctx, self.bits[:S], max_tokens=budget, stats=self.stats, payload_stride=stride,
+                             quality=self._rows(range(S)))
         stop = _StopCheck(self.p, sess, self.stop_text) if self.stop_text is not None else None
         if per_ctx:
             sess.park_slots(np.arange(S))
@@ -371,7 +378,7 @@ class SlotEncoder:
                     if pipelined:
                         pending = pin.take(sess.state)
                 key = _layout_key(logits, sess.state, sess.hist, sess.payload, lm.kv.table, lm.kv.lens,
-                                  sess.stats_acc) + (lm.kv.version,)
+                                  sess.stats_acc, sess.qtable) + (lm.kv.version,)
                 if self.use_graph:
                     if graph is None or key != gkey:
                         graph = None
@@ -396,11 +403,15 @@ class SlotEncoder:
         return tokens, (stats_out if self.stats else None)
 
     # ------------------------------------------------------------------
+    def _rows(self, msgs):
+        """The quality rows of messages ``msgs`` (None without per-message qualities)."""
+        return self.qual.take(list(msgs)) if self.qual is not None else None
+
     def _admit(self, sess, logits, first, slots, msgs, slot_msg, last_pos, last_move, t):
         import torch
 
         lm = self.lm
-        sess.load_slots(slots, [self.bits[m] for m in msgs])
+        sess.load_slots(slots, [self.bits[m] for m in msgs], quality=self._rows(msgs))
         lm.kv.reset(slots)
         idx = torch.as_tensor(np.asarray(slots, dtype=np.int64), device=logits.device)
         logits.index_copy_(0, idx, first.expand(len(slots), -1).to(logits.dtype))
@@ -427,7 +438,7 @@ class SlotEncoder:
         self.prefill_rows += lm.last_prefill["rows"]
         self.prefill_groups += lm.last_prefill["groups"]
         self.prefill_shared += lm.last_prefill["shared"]
-        sess.load_slots(slots, [self.bits[m] for m in msgs])
+        sess.load_slots(slots, [self.bits[m] for m in msgs], quality=self._rows(msgs))
         idx = torch.as_tensor(slots, device=logits.device)
         logits.index_copy_(0, idx, first.to(logits.dtype))
         slot_msg[slots] = msgs
@@ -479,8 +490,9 @@ class SlotDecoder:
 
     def __init__(self, provider, ctx, token_lists: Sequence[Sequence[int]], context: Sequence[int], *, slots: int,
                  use_graph: bool, check_every: int = 16, compact: bool = True,
-                 contexts: Optional[Sequence[Sequence[int]]] = None, share: bool = True):
+                 contexts: Optional[Sequence[Sequence[int]]] = None, share: bool = True, qualities=None):
         self.p, self.lm, self.ctx = provider, provider.lm, ctx
+        self.qual = qualities  # coder.StreamQuality with one row per message, or None
         self.lists = token_lists
         self.N = len(token_lists)
         self.S = max(1, min(int(slots), self.N))
@@ -499,7 +511,7 @@ class SlotDecoder:
 
         from .. import _lib as L
         from ..codec.errors import DecodeDivergenceError
-        from ..coder import _bit_rows_to_lists, _ptr, _state_tensor, _stream_handle
+        from ..coder import _bit_rows_to_lists, _ptr, _state_tensor, _stream_handle, _table_registered
 
         lm, S, N = self.lm, self.S, self.N
         lens_all = np.asarray([len(t) for t in self.lists], dtype=np.int64)
@@ -515,7 +527,8 @@ class SlotDecoder:
             first = lm.first_logits
         T0 = lm.kv.T0
         dev = logits.device
-        P = self.ctx.params.precision
+        qual = self.qual
+        P = qual.max_precision if qual is not None else self.ctx.params.precision  # the call's largest
         out_stride = int((Tcap * P + P + 7) // 8 + 8)
         st = {"tokmat": torch.zeros((S, Tcap), dtype=torch.int32, device=dev),
               "nlen": torch.zeros(S, dtype=torch.int32, device=dev),
@@ -524,6 +537,8 @@ class SlotDecoder:
               "out_bits": torch.zeros((S, out_stride), dtype=torch.uint8, device=dev)}
         if per_ctx:  # context rows of the message in each slot: the token index is lens - ctx (moves with compaction)
             st["ctx"] = torch.zeros(S, dtype=torch.int32, device=dev)
+        if qual is not None:  # the slots' quality rows (moves with compaction; every slot starts parked on a valid row)
+            st["quality"] = qual.take([0] * S).table(dev)
         ctx_host = np.full(S, T0, dtype=np.int64)
         self.ctx.check(L.lib().ns_init_state(self.ctx._h, _ptr(st["state"]), S, _stream_handle()), "ns_init_state")
         st["state"].view(torch.int32)[:, 7] = L.NS_ST_DONE
@@ -533,6 +548,7 @@ class SlotDecoder:
         out: List[Optional[List[int]]] = [None] * N
         init_row = torch.tensor([[0, 1 << P, 0, 0]], dtype=torch.int64, device=dev)
         p = self.ctx.params
+        k_max = qual.k_max if qual is not None else 0
         graph, gkey = None, None
         bufs = {}
         admit_blocked = False
@@ -544,10 +560,11 @@ class SlotDecoder:
             act = (tix < st["nlen"]).to(torch.uint8)
             last = (tix == st["nlen"] - 1).to(torch.uint8)
             bufs["tok"], bufs["act"], bufs["last"] = tok, act, last
-            rc = L.lib().ns_decode_step(self.ctx._h, _ptr(logits), logits.stride(0), st["state"].shape[0], _ptr(tok),
-                                        _ptr(last), _ptr(act), _ptr(st["state"]), _ptr(st["out_bits"]), out_stride,
-                                        float(p.temp), int(p.topk), self.ctx._banned, self.ctx._nbanned, None, 0,
-                                        _stream_handle())
+            with _table_registered(self.ctx, st.get("quality"), k_max):
+                rc = L.lib().ns_decode_step(self.ctx._h, _ptr(logits), logits.stride(0), st["state"].shape[0],
+                                            _ptr(tok), _ptr(last), _ptr(act), _ptr(st["state"]), _ptr(st["out_bits"]),
+                                            out_stride, float(p.temp), int(p.topk), self.ctx._banned,
+                                            self.ctx._nbanned, None, 0, _stream_handle())
             self.ctx.check(rc, "ns_decode_step")
             lm.step_static(tok)
 
@@ -660,8 +677,8 @@ class SlotDecoder:
                         ev_now = torch.cuda.Event()
                         ev_now.record()
                         pending = (ev_now, slot_msg.copy(), lm.kv.lens_host - ctx_host)
-                key = _layout_key(logits, st["state"], st["tokmat"], lm.kv.table, lm.kv.lens, st.get("ctx")) + \
-                    (lm.kv.version,)
+                key = _layout_key(logits, st["state"], st["tokmat"], lm.kv.table, lm.kv.lens, st.get("ctx"),
+                                  st.get("quality")) + (lm.kv.version,)
                 if self.use_graph:
                     if graph is None or key != gkey:
                         graph = None
@@ -727,7 +744,12 @@ class SlotDecoder:
         st["nlen"][idx] = nlt
         t0 = T0 if np.isscalar(T0) else torch.from_numpy(np.asarray(T0).astype(np.int32)).to(dev)
         st["stop"][idx] = nlt + (t0 - 1)
-        st["state"][idx] = init_row.expand(n, 4)
+        if self.qual is not None:  # the messages' quality rows, and fresh states at each row's 2^precision
+            rows = self.qual.take(list(msgs))
+            st["quality"][idx] = rows.table(dev)
+            st["state"][idx] = rows.init_rows(dev)
+        else:
+            st["state"][idx] = init_row.expand(n, 4)
         st["out_bits"][idx] = 0
         logits.index_copy_(0, idx, first.expand(n, -1).to(logits.dtype))
         slot_msg[slots] = msgs

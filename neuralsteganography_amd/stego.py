@@ -94,14 +94,31 @@ def packet_prefix(data: bytes) -> bytes:
     return text[:end].encode("utf-8")
 
 
-def _encode_streams(lm, bit_lists: List[List[int]], context: List[int], quality: Dict[str, Any]) -> List[List[int]]:
-    if hasattr(lm, "encode_batch"):
-        return lm.encode_batch(bit_lists, context, quality=quality)
-    return [lm.encode_arithmetic(bits, context, quality=quality) for bits in bit_lists]
+def _qkw(entry, quality) -> Dict[str, Any]:
+    """The quality keyword of a batched provider entry: ``quality`` (one dict), or ``qualities`` (a list, one per
+    stream) for a provider that takes it; None when the entry cannot take the list (the caller goes per stream)."""
+    if not isinstance(quality, list):
+        return {"quality": quality}
+    if all(q == quality[0] for q in quality):
+        return {"quality": quality[0] if quality else dict(DEFAULT_QUALITY)}
+    return {"qualities": quality} if _takes(entry, "qualities") else None
 
 
-def _decode_streams(lm, spans: List[List[int]], context: List[int], quality: Dict[str, Any]) -> List[List[int]]:
-    if hasattr(lm, "decode_batch"):
+def _q_at(quality, i: int):
+    return quality[i] if isinstance(quality, list) else quality
+
+
+def _encode_streams(lm, bit_lists: List[List[int]], context: List[int], quality) -> List[List[int]]:
+    """``quality``: one dict, or a list with one per stream (``qualities=`` of the batch front end)."""
+    kw = _qkw(getattr(lm, "encode_batch", None), quality) if hasattr(lm, "encode_batch") else None
+    if kw is not None:
+        return lm.encode_batch(bit_lists, context, **kw)
+    return [lm.encode_arithmetic(bits, context, quality=_q_at(quality, i)) for i, bits in enumerate(bit_lists)]
+
+
+def _decode_streams(lm, spans: List[List[int]], context: List[int], quality) -> List[List[int]]:
+    kw = _qkw(getattr(lm, "decode_batch", None), quality) if hasattr(lm, "decode_batch") else None
+    if kw is not None:
         if getattr(lm, "decodes_without_state", False):
             # the arithmetic coder decodes from the tokens alone: drop the queued states to stay aligned
             queue = getattr(lm, "_decode_states", None)
@@ -109,41 +126,60 @@ def _decode_streams(lm, spans: List[List[int]], context: List[int], quality: Dic
                 for _ in range(min(len(spans), len(queue))):
                     queue.popleft()
         # (a provider that needs its history, like the rank coder, pops its own states in decode_batch)
-        return lm.decode_batch(spans, context, quality=quality)
-    return [lm.decode_arithmetic(list(span), context, quality=quality) for span in spans]
+        return lm.decode_batch(spans, context, **kw)
+    return [lm.decode_arithmetic(list(span), context, quality=_q_at(quality, i)) for i, span in enumerate(spans)]
 
 
-def _encode_streams_each(lm, bit_lists: List[List[int]], contexts: List[List[int]],
-                         quality: Dict[str, Any]) -> List[List[int]]:
+def _encode_streams_each(lm, bit_lists: List[List[int]], contexts: List[List[int]], quality) -> List[List[int]]:
     """``_encode_streams`` with one context per stream (``seed_texts``).  A provider whose ``encode_batch`` takes
     one shared context only (the rank coder) is driven per packet, in order, as a provider without one is."""
-    if _takes_contexts(getattr(lm, "encode_batch", None)):
-        return lm.encode_batch(bit_lists, contexts=contexts, quality=quality)
-    return [lm.encode_arithmetic(bits, ctx, quality=quality) for bits, ctx in zip(bit_lists, contexts)]
+    kw = _qkw(getattr(lm, "encode_batch", None), quality) if _takes_contexts(getattr(lm, "encode_batch", None)) else None
+    if kw is not None:
+        return lm.encode_batch(bit_lists, contexts=contexts, **kw)
+    return [lm.encode_arithmetic(bits, ctx, quality=_q_at(quality, i))
+            for i, (bits, ctx) in enumerate(zip(bit_lists, contexts))]
 
 
-def _decode_streams_each(lm, spans: List[List[int]], contexts: List[List[int]],
-                         quality: Dict[str, Any]) -> List[List[int]]:
+def _decode_streams_each(lm, spans: List[List[int]], contexts: List[List[int]], quality) -> List[List[int]]:
     """``_decode_streams`` with one context per span (``seed_texts``)."""
-    if _takes_contexts(getattr(lm, "decode_batch", None)):
+    kw = _qkw(getattr(lm, "decode_batch", None), quality) if _takes_contexts(getattr(lm, "decode_batch", None)) else None
+    if kw is not None:
         if getattr(lm, "decodes_without_state", False):
             queue = getattr(lm, "_decode_states", None)
             if queue:
                 for _ in range(min(len(spans), len(queue))):
                     queue.popleft()
-        return lm.decode_batch(spans, contexts=contexts, quality=quality)
-    return [lm.decode_arithmetic(list(span), ctx, quality=quality) for span, ctx in zip(spans, contexts)]
+        return lm.decode_batch(spans, contexts=contexts, **kw)
+    return [lm.decode_arithmetic(list(span), ctx, quality=_q_at(quality, i))
+            for i, (span, ctx) in enumerate(zip(spans, contexts))]
 
 
-def _takes_contexts(entry) -> bool:
+def _takes(entry, name: str) -> bool:
     import inspect
 
     if entry is None:
         return False
     try:
-        return "contexts" in inspect.signature(entry).parameters
+        return name in inspect.signature(entry).parameters
     except (TypeError, ValueError):
         return False
+
+
+def _takes_contexts(entry) -> bool:
+    return _takes(entry, "contexts")
+
+
+def _message_qualities(quality, qualities, n: int):
+    """The merged quality of the call (``quality`` over :data:`DEFAULT_QUALITY`), or with ``qualities`` one merged
+    quality per message (the alias rules of ``quality``: the last top-k alias wins).  At most one of the two."""
+    if qualities is None:
+        return _quality_args(quality), None
+    if quality is not None:
+        raise ConfigurationError("give at most one of quality (shared) and qualities (one per message)")
+    qs = [_quality_args(q) for q in qualities]
+    if len(qs) != n:
+        raise ConfigurationError(f"{len(qs)} qualities for {n} messages")
+    return None, qs
 
 
 def _seed_contexts(lm, seed_texts: Sequence[str], n: int) -> List[List[int]]:
@@ -159,14 +195,18 @@ def _seed_contexts(lm, seed_texts: Sequence[str], n: int) -> List[List[int]]:
 
 def stego_encode_batch(messages: Sequence[bytes], *, chunk_bytes: int = 256, use_crc: bool = True,
                        ecc: Optional[str] = "rs", nsym: int = 10, quality: Optional[Dict[str, float]] = None,
+                       qualities: Optional[Sequence[Optional[Dict[str, float]]]] = None,
                        seed_text: str = "", seed_texts: Optional[Sequence[str]] = None, lm) -> List[EncodeResult]:
     """Every message -> its :class:`EncodeResult`; all packets of all messages are encoded as one batch.
+    ``qualities`` (one per message, as each ``stego_encode`` call of the reference has its own ``quality``): every
+    packet of message ``i`` is encoded with ``qualities[i]`` merged over :data:`DEFAULT_QUALITY`; ``quality`` is then
+    not given.
     ``seed_texts`` (one per message, as each ``stego_encode`` call of the reference has its own ``seed_text``):
     every packet of message ``i`` is encoded with ``encode_seed(seed_texts[i])``; ``seed_text`` is then unused."""
     per_msg = _seed_contexts(lm, seed_texts, len(messages)) if seed_texts is not None else None
     mode = normalise_ecc(ecc)
     cfg = {"chunk_bytes": int(chunk_bytes), "crc": bool(use_crc), "ecc": mode, "nsym": int(nsym if mode == "rs" else 0)}
-    q = _quality_args(quality)
+    q, per_q = _message_qualities(quality, qualities, len(messages))
     metas: List[EncodeMetadata] = []
     bit_lists: List[List[int]] = []
     owner: List[int] = []
@@ -177,6 +217,8 @@ def stego_encode_batch(messages: Sequence[bytes], *, chunk_bytes: int = 256, use
         for pkt in build_packets(chunks, msg_id=msg_id, cfg=cfg):
             bit_lists.append(bytes_to_bits_lsb(pkt))
             owner.append(mi)
+    if per_q is not None:
+        q = [per_q[mi] for mi in owner]
     if per_msg is not None:
         spans = _encode_streams_each(lm, bit_lists, [per_msg[mi] for mi in owner], q) if bit_lists else []
     else:
@@ -224,22 +266,26 @@ def _assemble(packets: List[Packet]) -> bytes:
 
 
 def stego_decode_batch(span_sets: Sequence[Iterable[List[int]]], *, use_crc: bool = True, ecc: Optional[str] = "rs",
-                       nsym: int = 10, quality: Optional[Dict[str, float]] = None, seed_text: str = "",
+                       nsym: int = 10, quality: Optional[Dict[str, float]] = None,
+                       qualities: Optional[Sequence[Optional[Dict[str, float]]]] = None, seed_text: str = "",
                        seed_texts: Optional[Sequence[str]] = None, lm, return_errors: bool = False) -> List[Any]:
     """Every message's spans -> its bytes, all spans decoded as one batch.  Errors (missing chunks, CRC, RS,
     cfg mismatch) raise for the first failing message, or are returned in its slot with
-    ``return_errors=True``.  ``seed_texts``: one seed text per message, as in :func:`stego_encode_batch`."""
+    ``return_errors=True``.  ``seed_texts``: one seed text per message, ``qualities``: one quality per message, as
+    in :func:`stego_encode_batch`."""
     span_sets = list(span_sets)
     per_msg = _seed_contexts(lm, seed_texts, len(span_sets)) if seed_texts is not None else None
     mode = normalise_ecc(ecc)
     expected = {"crc": bool(use_crc), "ecc": mode, "nsym": int(nsym if mode == "rs" else 0)}
-    q = _quality_args(quality)
+    q, per_q = _message_qualities(quality, qualities, len(span_sets))
     flat: List[List[int]] = []
     owner: List[int] = []
     for mi, spans in enumerate(span_sets):
         for span in spans:
             flat.append([int(t) for t in span])
             owner.append(mi)
+    if per_q is not None:
+        q = [per_q[mi] for mi in owner]
     if per_msg is not None:
         bits = _decode_streams_each(lm, flat, [per_msg[mi] for mi in owner], q) if flat else []
     else:
