@@ -145,6 +145,30 @@ int ns_seq_attention_ragged(const void* d_qkv, int64_t qkv_stride, void* d_out, 
                             const int32_t* d_seq_slot, int n_slots, int64_t layer_offset, int kv_format,
                             void* hip_stream);
 
+/* ns_seq_attention_ragged CONTINUED from KV pages: a context whose first rows another prefill already
+ * stored (a common prefix of different contexts, lm/kvpages.py) is run from its first new row on.
+ *   d_seq_past  int32 [n_seq], device: sequence s has d_seq_past[s] rows -- >= 0 and a multiple of 64 -- in the first
+ *               d_seq_past[s] / 32 pages of its table row; its d_seq_start[s + 1] - d_seq_start[s] packed rows are
+ *               its ABSOLUTE rows d_seq_past[s] .., and a d_blocks entry (s, j) names the 64 new queries from absolute
+ *               row d_seq_past[s] + 64 j.
+ * Key blocks below d_seq_past[s] / 64 are staged from the pages (16-byte loads of the bytes an earlier launch stored),
+ * the others from the packed rows; masks are absolute and the block order, the online softmax and the MFMA chains
+ * are those of ns_seq_attention_ragged (one body).  fp16 pages hold bit copies of the qkv values, so the output rows
+ * and the stored rows equal, bit for bit, those of the whole sequence run at once, and d_seq_past all zero gives
+ * ns_seq_attention_ragged's result.  New rows are stored at their absolute row (each (sequence, head, row) exactly
+ * once); pages below d_seq_past[s] / 32 are never written.
+ * Returns NS_ERR_UNSUPPORTED for NS_KV_FP8 (fp8 pages are converted values: no exact continuation exists) and
+ * NS_ERR_CONFIG for D != 64, a NULL d_page_table or a NULL d_seq_past.  A sequence whose d_seq_past is negative or no
+ * multiple of 64, whose past pages reach beyond max_chunks (or whose slot lies outside [0, n_slots)), or one of whose
+ * past table entries is zero or misaligned is skipped whole: no row or page of it is read, no output row and no page
+ * written. */
+int ns_seq_attention_ragged_past(const void* d_qkv, int64_t qkv_stride, void* d_out, int64_t out_stride,
+                                 const int32_t* d_seq_start, const int32_t* d_seq_past, int n_seq, int R,
+                                 const int32_t* d_blocks, int nblk, int H, int D, float scale,
+                                 const uint64_t* d_page_table, int64_t table_stride, int max_chunks,
+                                 const int32_t* d_seq_slot, int n_slots, int64_t layer_offset, int kv_format,
+                                 void* hip_stream);
+
 /* The head rows of one KV page into another, for many (source, destination) pairs in one launch: a context's KV
  * pages shared among the messages that carry it -- the context's last, partly filled page is copied into the first
  * own page of every holder, which that holder then appends into (a shared page is never an append target).

@@ -36,7 +36,7 @@ EXPORTS = ("ns_create", "ns_destroy", "ns_last_error", "ns_version", "ns_max_top
            "ns_lm_layernorm_count",
            "ns_lm_embed_ln", "ns_lm_embed_seq_ln", "ns_seq_attention", "ns_lm_ln_gemm",
            "ns_decode_attention_paged", "ns_lm_embed_ln_rows", "ns_lm_layernorm_rows", "ns_seq_attention_ragged",
-           "ns_kv_copy_rows",
+           "ns_kv_copy_rows", "ns_seq_attention_ragged_past",
            "ns_frac_create", "ns_frac_destroy", "ns_frac_last_error", "ns_frac_init", "ns_frac_encode_step",
            "ns_frac_decode_step", "ns_frac_set_slots", "ns_frac_scratch_bytes")
 NS_LM_EPI_STORE, NS_LM_EPI_GELU, NS_LM_EPI_RESIDUAL, NS_LM_EPI_STORE_F32 = 0, 1, 2, 3
@@ -192,6 +192,9 @@ def lib() -> ctypes.CDLL:
     L.ns_seq_attention_ragged.restype = ci
     L.ns_seq_attention_ragged.argtypes = [vp, i64, vp, i64, vp, ci, ci, vp, ci, ci, ci, ctypes.c_float, vp, i64, ci,
                                           vp, ci, i64, ci, vp]
+    L.ns_seq_attention_ragged_past.restype = ci
+    L.ns_seq_attention_ragged_past.argtypes = [vp, i64, vp, i64, vp, vp, ci, ci, vp, ci, ci, ci, ctypes.c_float, vp,
+                                               i64, ci, vp, ci, i64, ci, vp]
     L.ns_kv_copy_rows.restype = ci
     L.ns_kv_copy_rows.argtypes = [vp, vp, vp, ci, ci, i64, ci, ci, ci, vp]
     L.ns_frac_create.restype = vp

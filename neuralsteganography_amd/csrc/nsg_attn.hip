@@ -1101,6 +1101,7 @@ struct SeqStore {
     int max_chunks;
     int64_t layer_off;      // elements from a page's address to this layer's K block
     int64_t v_off;          // elements from the K block to the V block (H * 32 * D)
+    int past;               // PAST form only: absolute rows 0..past-1 of the sequence are already in its pages
 };
 
 // One workgroup: the 64 queries of block qb of ONE sequence of T rows, head columns at `base` (the sequence's first
@@ -1110,7 +1111,12 @@ struct SeqStore {
 // (kb == qb, rows < T) to the sequence's pages, fp16 copies / fp8 with the decode append's conversion (pack4_fp8
 // over 4 consecutive dims, as FmtF8::from_qkv) -- every (sequence, head, block) exactly once, from the registers
 // the staging holds anyway.
-template <int STORE>
+// PAST (ns_seq_attention_ragged_past, fp16 pages): the sequence's first ps.past rows (a multiple of 64, every entry of
+// table[0 .. past/32) checked by the caller) are in its pages and `base` / `obase` are its row ps.past; T and qb stay
+// ABSOLUTE (T = past + new rows, qb >= past/64).  Key blocks kb < past/64 are staged from pages 2kb and 2kb+1 -- the
+// bit copies an earlier launch stored there -- the others from the packed rows as ever; everything after the staging
+// is the one body, so a split at a multiple of 64 changes no bit of the output or of the stored rows.
+template <int STORE, bool PAST = false>
 __device__ __forceinline__ void seq_attn_block(const _Float16* __restrict__ base, int64_t qkv_stride,
                                                _Float16* __restrict__ obase, int64_t out_stride, int T, int qb, int h,
                                                int C, float scale_log2, const SeqStore& ps) {
@@ -1120,9 +1126,11 @@ __device__ __forceinline__ void seq_attn_block(const _Float16* __restrict__ base
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 15, c = lane >> 4;
     const int tq = qb * 64 + wave * 16 + r;  // this lane's query (padding rows past T are computed, not stored)
+    const int past = PAST ? ps.past : 0;     // packed row = absolute row - past
     f16x8 qf[2];
 #pragma unroll
-    for (int dc = 0; dc < 2; ++dc) qf[dc] = *(const f16x8*)(base + (int64_t)min(tq, T - 1) * qkv_stride + dc * 32 + c * 8);
+    for (int dc = 0; dc < 2; ++dc)
+        qf[dc] = *(const f16x8*)(base + (int64_t)(min(tq, T - 1) - past) * qkv_stride + dc * 32 + c * 8);
     sq_f32x4 o[4];
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) o[dt] = sq_f32x4{0.f, 0.f, 0.f, 0.f};
@@ -1134,9 +1142,17 @@ __device__ __forceinline__ void seq_attn_block(const _Float16* __restrict__ base
         for (int u = 0; u < 2; ++u) {
             const int id = (int)threadIdx.x + 256 * u;
             const int key = id >> 3, ch = id & 7;
-            const _Float16* src = base + (int64_t)min(kb * 64 + key, T - 1) * qkv_stride + ch * 8;
-            const f16x8 kv = *(const f16x8*)(src + C);
-            const f16x8 vv = *(const f16x8*)(src + 2 * C);
+            f16x8 kv, vv;
+            if (PAST && kb * 64 < past) {  // (uniform) a full block of stored rows: one 16-byte load per (key, chunk)
+                const _Float16* src = (const _Float16*)ps.table[2 * kb + (key >> 5)] + ps.layer_off +
+                                      (int64_t)h * 32 * ATT_D + (int64_t)(key & 31) * ATT_D + ch * 8;
+                kv = *(const f16x8*)src;
+                vv = *(const f16x8*)(src + ps.v_off);
+            } else {
+                const _Float16* src = base + (int64_t)(min(kb * 64 + key, T - 1) - past) * qkv_stride + ch * 8;
+                kv = *(const f16x8*)(src + C);
+                vv = *(const f16x8*)(src + 2 * C);
+            }
             *(f16x8*)(sK + key * 64 + ((ch ^ sq_swz(key)) * 8)) = kv;
             if constexpr (STORE != 0) {
                 const int row = kb * 64 + key;  // uniform test first: only the diagonal block's workgroup stores
@@ -1218,7 +1234,7 @@ __device__ __forceinline__ void seq_attn_block(const _Float16* __restrict__ base
     l += __shfl_xor(l, 32);
     if (tq >= T) return;
     const float inv = 1.0f / l;
-    _Float16* orow = obase + (int64_t)tq * out_stride;
+    _Float16* orow = obase + (int64_t)(tq - past) * out_stride;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) {
         sq_f16x4 v;
@@ -1270,6 +1286,43 @@ __global__ __launch_bounds__(256) void seq_attn_ragged_kernel(const _Float16* __
     }
     seq_attn_block<STORE>(qkv + (int64_t)r0 * qkv_stride + h * ATT_D, qkv_stride,
                           out + (int64_t)r0 * out_stride + h * ATT_D, out_stride, T, qb, h, H * ATT_D, scale_log2, ps);
+}
+
+// The ragged form continued from pages (ns_seq_attention_ragged_past, fp16 pages): sequence s has past[s] rows -- a
+// multiple of 64 -- in the first past[s] / 32 pages of its table row already, and its packed rows are its absolute
+// rows past[s] ..; list entry (s, j) is the 64 new queries from absolute row past[s] + 64 j.  On top of the ragged
+// form's guards the workgroup retires, before it reads a row or a page, when past[s] is negative or no multiple of 64,
+// when a past page lies at or beyond max_chunks (or the sequence has no table row), or when a past page's entry is
+// zero or misaligned: nothing is read through a bad entry.  past[s] == 0 runs the ragged form's instructions.
+__global__ __launch_bounds__(256) void seq_attn_ragged_past_kernel(
+    const _Float16* __restrict__ qkv, int64_t qkv_stride, _Float16* __restrict__ out, int64_t out_stride,
+    const int32_t* __restrict__ seq_start, const int32_t* __restrict__ seq_past, int n_seq, int R,
+    const int32_t* __restrict__ blocks, int H, float scale_log2, const uint64_t* __restrict__ table, int64_t tstride,
+    int max_chunks, const int32_t* __restrict__ seq_slot, int n_slots, int64_t layer_off) {
+    const int i = (int)(blockIdx.x / H), h = (int)(blockIdx.x % H);
+    const int s = blocks[2 * i], j = blocks[2 * i + 1];
+    if (s < 0 || s >= n_seq || j < 0) return;
+    const int r0 = seq_start[s], Tn = seq_start[s + 1] - r0, past = seq_past[s];
+    if (r0 < 0 || Tn < 1 || Tn > R - r0 || (int64_t)j * 64 >= Tn) return;
+    if (past < 0 || (past & 63) || (past >> 5) > max_chunks || (int64_t)past + Tn > 0x7FFFFFFF) return;
+    SeqStore ps{};
+    const int slot = seq_slot[s];
+    if (slot >= 0 && slot < n_slots) {  // (a slot outside the table: attention only, nothing stored)
+        ps.table = table + (int64_t)slot * tstride;
+        ps.max_chunks = max_chunks;
+    } else if (past > 0) {
+        return;
+    }
+    for (int p = 0; p < (past >> 5); ++p) {
+        const uint64_t pg = ps.table[p];
+        if (pg == 0 || (pg & 15u)) return;
+    }
+    ps.layer_off = layer_off;
+    ps.v_off = (int64_t)H * 32 * ATT_D;
+    ps.past = past;
+    seq_attn_block<1, true>(qkv + (int64_t)r0 * qkv_stride + h * ATT_D, qkv_stride,
+                            out + (int64_t)r0 * out_stride + h * ATT_D, out_stride, past + Tn, (past >> 6) + j, h,
+                            H * ATT_D, scale_log2, ps);
 }
 
 }  // namespace nsg
@@ -1512,6 +1565,33 @@ extern "C" int ns_seq_attention_ragged(const void* d_qkv, int64_t qkv_stride, vo
         hipLaunchKernelGGL(nsg::seq_attn_ragged_kernel<1>, grid, wg, 0, st, q, qkv_stride, o, out_stride, d_seq_start,
                            n_seq, R, d_blocks, H, sl2, d_page_table, table_stride, max_chunks, d_seq_slot, n_slots,
                            layer_offset);
+    return hipGetLastError() == hipSuccess ? NS_OK : NS_ERR_HIP;
+}
+
+extern "C" int ns_seq_attention_ragged_past(const void* d_qkv, int64_t qkv_stride, void* d_out, int64_t out_stride,
+                                            const int32_t* d_seq_start, const int32_t* d_seq_past, int n_seq, int R,
+                                            const int32_t* d_blocks, int nblk, int H, int D, float scale,
+                                            const uint64_t* d_page_table, int64_t table_stride, int max_chunks,
+                                            const int32_t* d_seq_slot, int n_slots, int64_t layer_offset,
+                                            int kv_format, void* hip_stream) {
+    if (!d_qkv || !d_out || !d_seq_start || !d_blocks || n_seq < 1 || R < n_seq || nblk < 1 || H < 1)
+        return NS_ERR_CONFIG;
+    if (D != nsg::ATT_D || !d_page_table || !d_seq_past) return NS_ERR_CONFIG;
+    if (kv_format == NS_KV_FP8) return NS_ERR_UNSUPPORTED;  // fp8 pages are no bit copies of the qkv rows
+    if (kv_format != NS_KV_FP16) return NS_ERR_CONFIG;
+    if (qkv_stride < 3LL * H * D || out_stride < (int64_t)H * D || (qkv_stride & 7) || (out_stride & 3) ||
+        (((uintptr_t)d_qkv | (uintptr_t)d_out) & 15u) ||
+        (((uintptr_t)d_seq_start | (uintptr_t)d_blocks | (uintptr_t)d_seq_past) & 3u))
+        return NS_ERR_CONFIG;
+    if (nblk > (R + 63) / 64 + n_seq) return NS_ERR_CONFIG;  // more entries than the R rows can have blocks
+    if ((int64_t)nblk * H > 0x7FFFFFFF) return NS_ERR_UNSUPPORTED;
+    if (!d_seq_slot || n_slots < 1 || max_chunks < 1 || table_stride < max_chunks || layer_offset < 0 ||
+        ((uintptr_t)d_page_table & 7u) || ((uintptr_t)d_seq_slot & 3u) || (layer_offset % 8))
+        return NS_ERR_CONFIG;
+    hipLaunchKernelGGL(nsg::seq_attn_ragged_past_kernel, dim3((unsigned)((int64_t)nblk * H)), dim3(256), 0,
+                       (hipStream_t)hip_stream, (const _Float16*)d_qkv, qkv_stride, (_Float16*)d_out, out_stride,
+                       d_seq_start, d_seq_past, n_seq, R, d_blocks, H, scale * 1.4426950408889634f, d_page_table,
+                       table_stride, max_chunks, d_seq_slot, n_slots, layer_offset);
     return hipGetLastError() == hipSuccess ? NS_OK : NS_ERR_HIP;
 }
 

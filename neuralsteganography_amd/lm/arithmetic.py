@@ -128,6 +128,9 @@ class HipArithmeticLM:
     slot_compaction = True  # native slot loops: compact the live slots once the queue is drained (off: tests that
                             # read per-step logits by row)
     share_contexts = True  # ``contexts=``: messages with equal contexts share the context's KV pages (off: A/B, tests)
+    # ``contexts=``: different contexts share the pages of a common prefix, in 64-token blocks (native
+    # path, fp16 pages and share_contexts on -- with an fp8 cache the call behaves as without it)
+    share_prefixes = True
 
     def __init__(self, model, tokenizer=None, *, device: Optional[str] = None, logits_dtype: str = "f32",
                  compute_dtype=None, banned: Optional[Sequence[int]] = None, max_batch: int = 4096,
@@ -289,7 +292,9 @@ class HipArithmeticLM:
         per conversation) is given.  With ``contexts`` a message's context is prefilled into its slot's own KV pages
         when it is admitted (``BatchedGPT2.prefill_contexts``); its tokens equal
         ``encode_batch([bits], contexts[m])[0]`` -- the receiver decodes it alone with that context.  Messages whose
-        contexts are equal share the context's KV pages and one prefill (``share_contexts``, ``lm/kvpages.py``).
+        contexts are equal share the context's KV pages and one prefill (``share_contexts``, ``lm/kvpages.py``);
+        different contexts that begin with the same 64-token blocks share the pages and the prefill of that beginning
+        (``share_prefixes``; fp16 pages only -- with ``kv_dtype="fp8"`` the call behaves as without it).
         All-equal ``contexts`` take the shared-context path; non-native LMs run their lockstep loop once per distinct
         context.
 
@@ -350,12 +355,14 @@ class HipArithmeticLM:
             enc = SlotEncoder(self, ctx, bit_lists, context, slots=S, finish=finish, stop_text=stop_text,
                               stats=return_stats, check_every=check_every, stall_steps=stall_steps, hard_cap=hard_cap,
                               use_graph=bool(graphs), compact=self.slot_compaction, contexts=contexts,
-                              share=self.share_contexts, qualities=sq)
+                              share=self.share_contexts, qualities=sq, share_prefixes=self.share_prefixes)
             toks, st = enc.run()
             self.last_schedule = {"slots": S, "evictions": enc.evictions, "compactions": enc.compactions,
                                   "max_live": enc.max_live, "kv_pages_peak": enc.kv_peak,
                                   "prefill_rows": enc.prefill_rows, "prefill_groups": enc.prefill_groups,
                                   "prefill_shared": enc.prefill_shared, "quality_groups": 1}
+            if enc.prefix_entries:  # (the key set stays as it was when no prefix is shared)
+                self.last_schedule.update(prefix_rows_saved=enc.prefix_rows_saved, prefix_entries=enc.prefix_entries)
             for b in bit_lists:
                 sc = _bits_count_state(len(b))
                 self._encode_states.append(sc)
@@ -462,11 +469,14 @@ class HipArithmeticLM:
             S = max(1, min(B, int(slots) if slots else self.max_batch))
             dec = SlotDecoder(self, self._coder(params, S, mixed=sq is not None), token_lists, context, slots=S,
                               use_graph=bool(graphs), compact=self.slot_compaction, contexts=contexts,
-                              share=self.share_contexts, qualities=sq)
+                              share=self.share_contexts, qualities=sq, share_prefixes=self.share_prefixes)
             out = dec.run()
             self.last_decode_schedule = {"slots": S, "evictions": dec.evictions, "compactions": dec.compactions,
                                          "prefill_rows": dec.prefill_rows, "prefill_groups": dec.prefill_groups,
                                          "prefill_shared": dec.prefill_shared, "quality_groups": 1}
+            if dec.prefix_entries:
+                self.last_decode_schedule.update(prefix_rows_saved=dec.prefix_rows_saved,
+                                                 prefix_entries=dec.prefix_entries)
             return out
         ctx = self._coder(params, B, mixed=sq is not None)
         sess = DecodeSession(ctx, token_lists, quality=sq)

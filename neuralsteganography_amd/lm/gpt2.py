@@ -131,6 +131,9 @@ class BatchedGPT2:
         self.prefill_row_budget = 65536
         self.last_prefill = None  # {"rows", "groups", "shared"} of the last prefill_contexts call
         self.share_contexts = True  # equal contexts of a call share their KV pages (off: A/B runs and tests)
+        # different contexts of a call share the pages of a common prefix, in 64-row blocks (lm/kvpages.py); in
+        # effect only with share_contexts on and fp16 pages (``prefix_sharing``)
+        self.share_prefixes = True
         # optional per-stream done flags read by the decode attention (int32 tensor view [B], bit 0 = finished, e.g.
         # the coder state's flags word): finished streams skip their cache reads; their logits are never used again
         self.done_flags = None
@@ -414,8 +417,18 @@ class BatchedGPT2:
         return h
 
     # ------------------------------------------------------------------ one context per stream (native path)
+    @property
+    def prefix_sharing(self) -> bool:
+        """Whether contexts share the pages of a common prefix: ``share_prefixes`` and ``share_contexts`` on the native
+        path with fp16 pages.  fp8 pages hold converted values while a whole prefill attends over the fp16 rows: a
+        prefill continued from them could not give the same bits, so it is not done."""
+        from .. import _lib
+
+        return bool(self.native and self.share_prefixes and self.share_contexts and
+                    self._kv_format == _lib.NS_KV_FP16)
+
     @torch.no_grad()
-    def prefill_contexts(self, contexts: Sequence[Sequence[int]], slots, shared=None) -> torch.Tensor:
+    def prefill_contexts(self, contexts: Sequence[Sequence[int]], slots, shared=None, chains=None) -> torch.Tensor:
         """Run one context PER stream and leave each in its stream's own KV pages: ``contexts[i]`` (trimmed to its
         last 1,022 ids as :meth:`prefill` trims) becomes positions ``0..T_i-1`` of slot ``slots[i]`` of a call begun
         with ``begin_slots(B, 0, ...)`` (pages for those positions are mapped here unless the caller already has).
@@ -435,7 +448,18 @@ class BatchedGPT2:
         full pages, the context's last partial page is copied into the holder's first own page (``ns_kv_copy_rows``:
         the holder appends into it) and its logits row is the entry's.  The stored bytes are the ones a private
         prefill stores and the decode step reads by address, so the bits do not change.  ``last_prefill`` has the
-        ``rows`` actually run, the ``groups`` they ran in and ``shared``, the slots served from an entry."""
+        ``rows`` actually run, the ``groups`` they ran in and ``shared``, the slots served from an entry.
+
+        Different contexts share the pages of a common prefix (``prefix_sharing``; ``chains``: one chain of
+        :func:`kvpages.plan_prefixes` per context, from a scheduler that planned the whole call -- default: planned
+        over this call's contexts, and none when ``shared`` is given without it).  The prefix entries that are new run
+        first, level by level, parents before children, each over its own rows only; then every context's remaining
+        rows -- an equal-context entry's, a private suffix's or a singleton's -- at positions ``past + index`` through
+        ``ns_seq_attention_ragged_past``, which takes the key blocks below ``past`` from the chain's pages.  A split at
+        a multiple of 64 changes no bit (the kernel's contract), the other kernels are row-wise, and a context's
+        logits row is its last new row's: row ``i`` still equals ``prefill(contexts[i], 1, ...)``.  A run in which
+        every ``past`` is 0 calls ``ns_seq_attention_ragged`` as before.  When a prefix was shared ``last_prefill``
+        also has ``prefix_rows_saved``, the rows not run for it, and ``prefix_entries``, the prefix entries run."""
         if not self.native:
             raise RuntimeError("prefill_contexts needs the native HIP path (fp16 on the GPU)")
         kv = self.kv
@@ -455,13 +479,25 @@ class BatchedGPT2:
                 raise ValueError(f"context token ids must lie in [0, {self.shape.vocab})")
         from ..exceptions import KVCapacityError
 
+        from .kvpages import plan_prefixes
+
         lens = np.asarray([len(c) for c in ctxs], dtype=np.int64)
+        # only slots that can take a hold (no page mapped yet) or have one are compared: a context whose twin keeps
+        # private pages stays a singleton, it does not open an entry for itself alone
+        el = [i for i, s in enumerate(slots.tolist())
+              if kv.nch[s] == 0 or kv.slot_entry[s] is not None or kv.slot_prefix[s] is not None]
+        if chains is None:
+            chains = [()] * n
+            if shared is None and self.prefix_sharing and len(el) > 1:
+                for i, ch in zip(el, plan_prefixes([ctxs[i] for i in el])):
+                    chains[i] = ch
+        elif len(chains) != n:
+            raise ValueError("one prefix chain per context")
+        elif any(chains) and not self.prefix_sharing:
+            raise ValueError("prefix chains need prefix_sharing (fp16 pages, share_contexts and share_prefixes)")
         if shared is None:  # a context shares when a live entry holds it or another context of this call equals it
             from .kvpages import sharing_keys
 
-            # only slots that can take a hold (no page mapped yet) or have one are compared: a context whose twin
-            # keeps private pages stays a singleton, it does not open an entry for itself alone
-            el = [i for i, s in enumerate(slots.tolist()) if kv.nch[s] == 0 or kv.slot_entry[s] is not None]
             keys = [None] * n
             if self.share_contexts and el:
                 for i, k in zip(el, sharing_keys([ctxs[i] for i in el], kv.entries)):
@@ -472,53 +508,86 @@ class BatchedGPT2:
             if sh.size != n:
                 raise ValueError("one shared flag per context")
             keys = [tuple(c) if f else None for c, f in zip(ctxs, sh)]
-        # holders: their table rows start with the entry's full pages (a scheduler may have mapped them already)
-        todo = [i for i in np.nonzero(sh)[0].tolist() if kv.slot_entry[slots[i]] is None]
-        if todo and kv.hold(slots[todo], [keys[i] for i in todo], lens[todo]).size:
+        # holders: their table rows start with the chain's and the entry's full pages (a scheduler may have mapped them)
+        # (a call of unrelated contexts has nothing held: the loops below run over the holders only)
+        held = [i for i, s in enumerate(slots.tolist()) if sh[i] or chains[i] or kv.slot_prefix[s] is not None]
+        todo = [i for i in held if kv.slot_entry[slots[i]] is None and kv.slot_prefix[slots[i]] is None]
+        if todo and kv.hold(slots[todo], [keys[i] for i in todo], lens[todo], [chains[i] for i in todo]).size:
             kv.release(slots[todo])
             raise KVCapacityError("no device memory for a shared context's KV pages")
-        for i in np.nonzero(sh)[0].tolist():
-            if kv.slot_entry[slots[i]].key != keys[i]:
-                raise RuntimeError("prefill_contexts: the slot holds another context")
+        past = np.zeros(n, dtype=np.int64)  # rows a slot's own run skips: its private suffix starts there
+        for i in held:
+            e, p = kv.slot_entry[slots[i]], kv.slot_prefix[slots[i]]
+            if sh[i]:
+                if e is None or e.key != keys[i]:
+                    raise RuntimeError("prefill_contexts: the slot holds another context")
+            elif p is not None:
+                if p.T >= lens[i] or tuple(ctxs[i][: p.T]) != p.key:
+                    raise RuntimeError("prefill_contexts: the slot holds another prefix")
+                past[i] = p.T
         if kv.ensure(slots, lens).size:  # (a scheduler has mapped them already, with room for its next steps)
             kv.release(slots[todo])  # the holds taken above: no entry stays behind unprefilled
             raise KVCapacityError("no device memory for the contexts' KV pages")
         kv.set_lens(slots, lens)
         out = torch.empty((n, self.ld), device=self.device, dtype=self.logits_dtype)
-        rows = ngroups = 0
-        # new entries: each prefilled once, through a table of its own pages
-        new = [e for e in {id(kv.slot_entry[slots[i]]): kv.slot_entry[slots[i]] for i in np.nonzero(sh)[0]}.values()
-               if e.logits is None]
-        if new:
-            etab = np.zeros((len(new), max(e.pages.size for e in new)), dtype=np.int64)
-            for j, e in enumerate(new):
-                etab[j, : e.pages.size] = e.pages
+        rows = ngroups = saved = 0
+        # new entries: each prefilled once, through a table of its chain's and its own pages -- the prefix entries
+        # level by level, parents first, then the equal-context entries
+        stages, seen = {}, set()
+        for i in held:
+            e = kv.slot_entry[slots[i]] or kv.slot_prefix[slots[i]]
+            line = []
+            while e is not None:
+                line.append(e)
+                e = e.parent
+            for depth, e in enumerate(reversed(line)):
+                if id(e) not in seen and not (e.ready if e.is_prefix else e.logits is not None):
+                    seen.add(id(e))
+                    stages.setdefault(depth if e.is_prefix else 1 << 30, []).append(e)
+        nprefix = 0
+        for depth in sorted(stages):
+            new = stages[depth]
+            tabs = [e.table_pages(tail=True) for e in new]
+            etab = np.zeros((len(new), max(t.size for t in tabs)), dtype=np.int64)
+            for j, t in enumerate(tabs):
+                etab[j, : t.size] = t
             d_etab = torch.from_numpy(etab).to(self.device)
-            elens = [e.T for e in new]
+            elens = [e.T - e.past for e in new]
             for a, b in prefill_groups(elens, self.prefill_row_budget):
-                lg = self._prefill_group([list(e.key) for e in new[a:b]], np.arange(a, b), d_etab)
+                lg = self._prefill_group([list(e.key[e.past:]) for e in new[a:b]], np.arange(a, b), d_etab,
+                                         past=np.asarray([e.past for e in new[a:b]], dtype=np.int64),
+                                         logits=not new[a].is_prefix)
                 for j, e in enumerate(new[a:b]):
-                    e.logits = lg[j:j + 1].clone()
+                    e.ready = True
+                    if not e.is_prefix:
+                        e.logits = lg[j:j + 1].clone()
                 ngroups += 1
             rows += int(sum(elens))
-        # singletons: straight into their slots' own pages
+            if new[0].is_prefix:
+                nprefix += len(new)
+            else:
+                saved += int(sum(e.past for e in new))
+        # singletons and private suffixes: straight into their slots' own pages
         single = np.nonzero(~sh)[0]
         if single.size:
-            for a, b in prefill_groups(lens[single], self.prefill_row_budget):
+            for a, b in prefill_groups(lens[single] - past[single], self.prefill_row_budget):
                 ix = single[a:b]
-                lg = self._prefill_group([ctxs[i] for i in ix], slots[ix])
+                lg = self._prefill_group([ctxs[i][past[i]:] for i in ix], slots[ix], past=past[ix])
                 if single.size == n:  # nothing shared: consecutive rows of the result
                     out[a:b] = lg
                 else:
                     out[torch.from_numpy(ix).to(self.device)] = lg
                 ngroups += 1
-            rows += int(lens[single].sum())
+            rows += int((lens[single] - past[single]).sum())
+            saved += int(past[single].sum())
         # holders: the master tail's rows into the first own page, the entry's logits into the slot's row
         hold = np.nonzero(sh)[0]
         if hold.size:
             self._copy_tails(slots[hold])
             out[torch.from_numpy(hold).to(self.device)] = torch.cat([kv.slot_entry[slots[i]].logits for i in hold])
         self.last_prefill = {"rows": rows, "groups": ngroups, "shared": int(hold.size)}
+        if past.any() or any(kv.slot_entry[slots[i]].parent is not None for i in hold):
+            self.last_prefill.update(prefix_rows_saved=saved, prefix_entries=nprefix)
         return out
 
     def _copy_tails(self, slots: np.ndarray) -> None:
@@ -535,9 +604,12 @@ class BatchedGPT2:
                                           s.n_layer, kv.pool.layer_offset(1), s.n_head, s.n_embd // s.n_head,
                                           self._kv_format, _stream_handle()), "ns_kv_copy_rows")
 
-    def _prefill_group(self, ctxs: List[List[int]], slots: np.ndarray, table: torch.Tensor = None) -> torch.Tensor:
+    def _prefill_group(self, ctxs: List[List[int]], slots: np.ndarray, table: torch.Tensor = None, past=None,
+                       logits: bool = True) -> torch.Tensor:
         """One ragged run of ``ctxs`` storing K/V through rows ``slots`` of ``table`` (default: the call's page
-        table); returns the logits after each context's last token."""
+        table); returns the logits after each context's last token (None with ``logits`` False).  ``past``: rows of
+        each sequence that its table row's first pages hold already -- ``ctxs[i]`` are then the tokens from position
+        ``past[i]`` on; a run with a nonzero ``past`` goes through ``ns_seq_attention_ragged_past``."""
         from .. import _lib
         from ..coder import _stream_handle
 
@@ -551,7 +623,10 @@ class BatchedGPT2:
         seq_start, blocks = ragged_blocks(lens)
         R, n = int(seq_start[-1]), len(ctxs)
         tok = torch.from_numpy(np.concatenate([np.asarray(c, dtype=np.int32) for c in ctxs])).to(dev)
-        pos = torch.from_numpy(np.concatenate([np.arange(t, dtype=np.int32) for t in lens])).to(dev)
+        past = np.zeros(len(ctxs), dtype=np.int32) if past is None else np.asarray(past, dtype=np.int32)
+        pos = np.concatenate([np.arange(p, p + t, dtype=np.int32) for p, t in zip(past, lens)])  # past + index
+        pos = torch.from_numpy(pos).to(dev)
+        d_past = torch.from_numpy(past).to(dev) if past.any() else None
         d_start = torch.from_numpy(seq_start).to(dev)
         d_blocks = torch.from_numpy(blocks).to(dev)
         d_slot = torch.from_numpy(slots.astype(np.int32)).to(dev)
@@ -564,6 +639,15 @@ class BatchedGPT2:
                    "ns_lm_embed_ln_rows")
 
         def attention(i, qkv, o):
+            if d_past is not None:  # continued from the pages of a shared prefix
+                _check(L.ns_seq_attention_ragged_past(qkv.data_ptr(), qkv.stride(0), o.data_ptr(), o.stride(0),
+                                                      d_start.data_ptr(), d_past.data_ptr(), n, R,
+                                                      d_blocks.data_ptr(), blocks.shape[0], H, D, 1.0 / math.sqrt(D),
+                                                      table.data_ptr(), table.stride(0), table.shape[1],
+                                                      d_slot.data_ptr(), table.shape[0], kv.pool.layer_offset(i),
+                                                      self._kv_format, st),
+                       "ns_seq_attention_ragged_past")
+                return
             _check(L.ns_seq_attention_ragged(qkv.data_ptr(), qkv.stride(0), o.data_ptr(), o.stride(0),
                                              d_start.data_ptr(), n, R, d_blocks.data_ptr(), blocks.shape[0], H, D,
                                              1.0 / math.sqrt(D), table.data_ptr(), table.stride(0), table.shape[1],
@@ -572,6 +656,8 @@ class BatchedGPT2:
                    "ns_seq_attention_ragged")
 
         hs = self._rows_native(R, embed, attention)
+        if not logits:
+            return None
         last = torch.from_numpy((seq_start[1:] - 1).astype(np.int64)).to(dev)
         return self._head_native(hs.index_select(0, last))
 

@@ -29,6 +29,19 @@ a MASTER TAIL page that no slot ever appends into.  A holder's table row has the
 slot's own pages only and drops its hold; the entry's pages go back to the pool with its last holder, and nothing is
 kept for later.  ``in_use`` / ``peak`` count physical pages (a shared page once); ``nch`` counts table columns.
 
+SHARED PREFIXES.  Different contexts of a call that begin with the same tokens share the pages of
+that beginning, in units of 64 rows (two pages: the key block of the prefill's attention, which is what keeps the bits
+equal -- ``ns_seq_attention_ragged_past``).  :func:`plan_prefixes` builds a trie over the 64-token blocks of the
+call's distinct contexts; a PREFIX ENTRY (``PagedKV.prefixes``, keyed by the tokens up to its end) is a maximal run of
+blocks that one set of at least two distinct contexts passes through, its ``parent`` the run before it, and a
+context's ``past`` -- the rows it does not prefill -- is the end of its deepest run, always below its length.  A
+prefix entry owns its own run's pages only (all full: no master tail, no copy); an equal-context entry may have a
+prefix parent and then owns the pages after it.  A holder's table row is the chain's pages in order, then the
+equal-context entry's full pages if there is one, then its own.  Entries count their holders -- slots, and the
+entries opened beneath them -- so holds and releases walk the chain and an entry's pages return to the pool with its
+last holder.  A chain is at most ``MAX_PREFIX_DEPTH`` = 2 runs deep; what a context shares beyond them stays private.
+fp8 pages hold converted values, not the bits a whole prefill attends over, so prefixes are shared with fp16 pages only.
+
 The host keeps a mirror of the table and of the lengths (every slot advances one position per step), so page
 bookkeeping needs no device read.  Pure host logic over torch tensors: the CPU tests drive it with CPU tensors.
 """
@@ -41,6 +54,8 @@ import numpy as np
 import torch
 
 PAGE_ROWS = 32
+PREFIX_ROWS = 64  # a shared prefix ends on a key block of the prefill's attention (two pages)
+MAX_PREFIX_DEPTH = 2  # prefix entries on one context's chain
 
 
 class KVPagePool:
@@ -149,15 +164,33 @@ class KVPagePool:
 class SharedContext:
     """One context's KV pages held by several slots of a call (see the module docstring): ``pages`` are its
     ``ceil(T / 32)`` page addresses (the last one the master tail when ``tail_rows > 0``), ``logits`` the ``[1, ld]``
-    row after the context's last token (None until the entry has been prefilled), ``holders`` the slots holding it."""
+    row after the context's last token (None until the entry has been prefilled), ``holders`` the slots holding it.
 
-    __slots__ = ("key", "T", "pages", "full", "tail_rows", "logits", "holders")
+    With a ``parent`` (a prefix entry) the entry owns rows ``past .. T-1`` only, ``past`` = the parent's
+    ``T``: ``pages`` are the ``ceil(T / 32) - past / 32`` pages after the parent's, ``full`` counts the full ones among
+    them and ``base`` the table columns before them.  A PREFIX entry (``is_prefix``: rows ``past .. T-1`` of every
+    context that begins with ``key``, both multiples of 64) has full pages only and no logits; ``ready`` says its rows
+    have been prefilled.  ``holders`` counts slots and the entries opened beneath this one."""
 
-    def __init__(self, key, T: int, pages: np.ndarray):
+    __slots__ = ("key", "T", "pages", "full", "tail_rows", "logits", "holders", "parent", "past", "is_prefix", "ready")
+
+    def __init__(self, key, T: int, pages: np.ndarray, parent: "SharedContext" = None, is_prefix: bool = False):
         self.key, self.T, self.pages = key, int(T), pages
-        self.full, self.tail_rows = self.T // PAGE_ROWS, self.T % PAGE_ROWS
+        self.parent, self.past = parent, (parent.T if parent is not None else 0)
+        self.full, self.tail_rows = (self.T - self.past) // PAGE_ROWS, self.T % PAGE_ROWS
+        self.is_prefix, self.ready = bool(is_prefix), False
         self.logits = None
         self.holders = 0
+
+    @property
+    def base(self) -> int:
+        """Table columns before this entry's pages (its chain's)."""
+        return self.past // PAGE_ROWS
+
+    def table_pages(self, tail: bool = False) -> np.ndarray:
+        """The chain's pages in order, then this entry's full pages (``tail``: its master tail too)."""
+        own = self.pages if tail else self.pages[: self.full]
+        return own if self.parent is None else np.concatenate([self.parent.table_pages(), own])
 
 
 def sharing_keys(contexts, entries=()):
@@ -180,16 +213,69 @@ def sharing_keys(contexts, entries=()):
     return [k if k is not None and (count[k] > 1 or k in entries) else None for k in keys]
 
 
-def shared_pages(T: int) -> int:
-    """Pages a shared context of ``T`` rows owns: its full pages and the master tail."""
-    return (int(T) + PAGE_ROWS - 1) // PAGE_ROWS
+def plan_prefixes(contexts):
+    """For every (trimmed) context of a call its CHAIN of shared prefix runs, outermost first: a tuple of
+    ``(key, start, end)`` -- rows ``start .. end-1`` (multiples of 64) of every context that begins with ``key``, the
+    context's first ``end`` ids -- or ``()`` when it shares no prefix.  A run is a maximal stretch of 64-token blocks
+    that one set of at least 2 DISTINCT contexts passes through (a context passes through the blocks that end below
+    its length: one new row always remains); at most ``MAX_PREFIX_DEPTH`` runs per chain, the rest stays private.  A
+    context of 64 tokens or fewer has none.  Only contexts whose first block looks like another's (ids 0, 31 and 63)
+    enter the trie: a call of unrelated contexts pays a few operations per context."""
+    chains = [()] * len(contexts)
+
+    def sig(c):
+        return (c[0], c[31], c[63])
+
+    seen = {}
+    for c in contexts:
+        if len(c) > PREFIX_ROWS:
+            g = sig(c)
+            seen[g] = seen.get(g, 0) + 1
+    distinct = {}
+    for i, c in enumerate(contexts):
+        if len(c) > PREFIX_ROWS and seen[sig(c)] > 1:
+            distinct.setdefault(tuple(c), []).append(i)
+    if len(distinct) < 2:
+        return chains
+    nodes, paths = {}, []  # (parent node, block) -> [node id, distinct contexts through it]
+    for c in distinct:
+        pid, path = 0, []
+        for k in range((len(c) - 1) // PREFIX_ROWS):
+            node = nodes.setdefault((pid, c[PREFIX_ROWS * k: PREFIX_ROWS * (k + 1)]), [len(nodes) + 1, 0])
+            node[1] += 1
+            pid = node[0]
+            path.append(node)
+        paths.append(path)
+    for (c, who), path in zip(distinct.items(), paths):
+        chain, k = [], 0
+        while k < len(path) and path[k][1] >= 2 and len(chain) < MAX_PREFIX_DEPTH:
+            j = k
+            while j < len(path) and path[j][1] == path[k][1]:  # the same set: sets only shrink along a path
+                j += 1
+            chain.append((c[: PREFIX_ROWS * j], PREFIX_ROWS * k, PREFIX_ROWS * j))
+            k = j
+        for i in who:
+            chains[i] = tuple(chain)
+    return chains
 
 
-def own_pages(T: int, ahead: int, shares: bool) -> int:
+def chain_past(chain) -> int:
+    """Rows a context with this chain does not prefill: the end of its deepest shared run."""
+    return int(chain[-1][2]) if chain else 0
+
+
+def shared_pages(T: int, past: int = 0) -> int:
+    """Pages a shared context of ``T`` rows owns: its full pages and the master tail (after its prefix parent's
+    ``past`` rows, if it has one); a prefix run of rows ``past .. T-1`` owns ``(T - past) / 32``."""
+    return (int(T) + PAGE_ROWS - 1) // PAGE_ROWS - int(past) // PAGE_ROWS
+
+
+def own_pages(T: int, ahead: int, shares: bool, past: int = 0) -> int:
     """Pages a message with a ``T``-row context maps for itself up to position ``T + ahead``: all of them, or, when it
-    shares the context, those after the context's full pages."""
+    shares the context, those after the context's full pages, or, when it shares a prefix of ``past`` rows only,
+    those after the prefix."""
     need = (int(T) + int(ahead) + PAGE_ROWS - 1) // PAGE_ROWS
-    return need - int(T) // PAGE_ROWS if shares else need
+    return need - int(T) // PAGE_ROWS if shares else need - int(past) // PAGE_ROWS
 
 
 class PagedKV:
@@ -213,7 +299,9 @@ class PagedKV:
         self.in_use = 0  # physical pages mapped now (a shared page once), and the most at once in this call
         self.peak = 0
         self.entries = {}  # trimmed context (tuple) -> SharedContext, while at least one slot holds it
+        self.prefixes = {}  # a shared prefix's tokens (tuple) -> its SharedContext, while anything holds it
         self.slot_entry: List[Optional[SharedContext]] = [None] * self.B
+        self.slot_prefix: List[Optional[SharedContext]] = [None] * self.B  # a private suffix's deepest prefix entry
         self.nshared = np.zeros(self.B, dtype=np.int64)  # leading table columns that are an entry's pages
 
     # ------------------------------------------------------------------
@@ -270,34 +358,45 @@ class PagedKV:
         dev = self.table.device
         self.table[torch.from_numpy(rows).to(dev), torch.from_numpy(cols).to(dev)] = torch.from_numpy(pages).to(dev)
 
-    def hold(self, slots, keys, lens) -> np.ndarray:
+    def hold(self, slots, keys, lens, chains=None) -> np.ndarray:
         """Let every slot in ``slots`` (released, no page mapped) hold the shared context ``keys[i]`` of ``lens[i]``
         rows: the entry is opened if no slot holds it yet (its pages taken from the pool; its ``logits`` stay None
         until the caller has prefilled it), and its full pages become the slot's first table columns.  The slot's own
-        pages follow through :meth:`ensure`.  Returns the slots whose entry could not be opened (the pool is out of
-        memory); nothing is mapped for them."""
+        pages follow through :meth:`ensure`.  ``chains[i]`` (:func:`plan_prefixes`) names the context's shared prefix
+        runs: those not live are opened with the entry (``ready`` False until prefilled), each the parent of the
+        next and the last the parent of the context's entry; with ``keys[i]`` None the slot holds the deepest run
+        itself and its private suffix follows in its own pages.  The table row is the chain's pages, then the entry's.
+        Returns the slots for which something could not be opened (the pool is out of memory); nothing is mapped for
+        them."""
         slots = np.asarray(slots, dtype=np.int64).reshape(-1)
         failed, rows, cols, pages = [], [], [], []
-        for s, key, T in zip(slots.tolist(), keys, np.asarray(lens, dtype=np.int64).reshape(-1).tolist()):
-            if self.nch[s] or self.slot_entry[s] is not None:
+        lens = np.asarray(lens, dtype=np.int64).reshape(-1).tolist()
+        for i, (s, key, T) in enumerate(zip(slots.tolist(), keys, lens)):
+            if self.nch[s] or self.slot_entry[s] is not None or self.slot_prefix[s] is not None:
                 raise RuntimeError("hold: the slot still has pages")
-            e = self.entries.get(key)
+            e = self.entries.get(key) if key is not None else None
             if e is None:
-                p = self.pool.take(shared_pages(T))
-                if p is None:
+                chain = chains[i] if chains is not None else ()
+                if key is None and not chain:
+                    raise ValueError("hold: neither a shared context nor a shared prefix")
+                if chain and chain[-1][2] >= T:
+                    raise ValueError("hold: a shared prefix must end below the context's length")
+                e = self._open(key, T, chain)
+                if e is None:
                     failed.append(s)
                     continue
-                e = self.entries[key] = SharedContext(key, T, p)
-                self.in_use += int(p.size)
-                self.peak = max(self.peak, self.in_use)
             elif e.T != T:
                 raise ValueError("hold: the context's length differs from its entry's")
             e.holders += 1
-            self.slot_entry[s] = e
-            self.nshared[s] = self.nch[s] = e.full
-            rows.append(np.full(e.full, s, dtype=np.int64))
-            cols.append(np.arange(e.full, dtype=np.int64))
-            pages.append(e.pages[: e.full])
+            if e.is_prefix:
+                self.slot_prefix[s] = e
+            else:
+                self.slot_entry[s] = e
+            tp = e.table_pages()
+            self.nshared[s] = self.nch[s] = tp.size
+            rows.append(np.full(tp.size, s, dtype=np.int64))
+            cols.append(np.arange(tp.size, dtype=np.int64))
+            pages.append(tp)
         if rows:
             rows, cols, pages = np.concatenate(rows), np.concatenate(cols), np.concatenate(pages)
             if rows.size:
@@ -309,6 +408,37 @@ class PagedKV:
                     torch.from_numpy(pages).to(dev)
         return np.asarray(failed, dtype=np.int64)
 
+    def _open(self, key, T: int, chain) -> Optional[SharedContext]:
+        """Open what a holder of context ``key`` (None: a private suffix) with ``chain`` needs and nothing holds yet
+        -- the chain's runs that are not live, then the context's entry -- with ONE take from the pool (all or
+        nothing).  Returns the entry the holder holds (no hold counted yet), or None if the pool is short."""
+        todo, past = [], 0
+        for k, a, b in chain:
+            p = self.prefixes.get(k)
+            if a != past or b <= a or b % PREFIX_ROWS or (p is not None and (p.past, p.T) != (a, b)):
+                raise ValueError("hold: the shared prefix chain does not fit its live entries")
+            if p is None:
+                todo.append((k, b, a, True))
+            past = b
+        if key is not None:
+            todo.append((key, T, past, False))
+        taken = self.pool.take(sum(shared_pages(t, a) for _, t, a, _ in todo))
+        if taken is None:
+            return None
+        self.in_use += int(taken.size)
+        self.peak = max(self.peak, self.in_use)
+        live = len(chain) - sum(1 for t in todo if t[3])  # live runs are the chain's head: a run holds its parent
+        e = self.prefixes[chain[live - 1][0]] if live else None
+        for k, t, a, is_prefix in todo:
+            n = shared_pages(t, a)
+            child = SharedContext(k, t, taken[:n], parent=e, is_prefix=is_prefix)
+            taken = taken[n:]
+            if e is not None:
+                e.holders += 1
+            (self.prefixes if is_prefix else self.entries)[k] = child
+            e = child
+        return e
+
     def tail_copies(self, slots):
         """``(src, dst, rows)`` for ``ns_kv_copy_rows``: for every holder in ``slots`` whose context ends inside a
         page, the entry's master tail page, the slot's first own page (mapped) and the rows to copy."""
@@ -317,10 +447,10 @@ class PagedKV:
             e = self.slot_entry[s]
             if e is None or e.tail_rows == 0:
                 continue
-            if self.nch[s] <= e.full:
+            if self.nch[s] <= e.base + e.full:
                 raise RuntimeError("tail_copies: the holder's first own page is not mapped")
             src.append(int(e.pages[e.full]))
-            dst.append(int(self.host[s, e.full]))
+            dst.append(int(self.host[s, e.base + e.full]))
             rows.append(e.tail_rows)
         return (np.asarray(src, dtype=np.int64), np.asarray(dst, dtype=np.int64), np.asarray(rows, dtype=np.int32))
 
@@ -341,15 +471,16 @@ class PagedKV:
         self.nch[slots] = 0
         self.nshared[slots] = 0
         for s in slots.tolist():
-            e = self.slot_entry[s]
-            if e is None:
-                continue
-            self.slot_entry[s] = None
-            e.holders -= 1
-            if e.holders == 0:  # nothing is kept for later: the page budget stays exact
-                self.pool.give(e.pages)
+            e = self.slot_entry[s] or self.slot_prefix[s]
+            self.slot_entry[s] = self.slot_prefix[s] = None
+            while e is not None:  # up the chain while an entry loses its last holder
+                e.holders -= 1
+                if e.holders:
+                    break
+                self.pool.give(e.pages)  # nothing is kept for later: the page budget stays exact
                 self.in_use -= int(e.pages.size)
-                del self.entries[e.key]
+                del (self.prefixes if e.is_prefix else self.entries)[e.key]
+                e = e.parent
 
     def reset(self, slots, lens=None) -> None:
         """``release`` + the slots' cache lengths back to the shared context (a new message starts there), or to
@@ -394,5 +525,6 @@ class PagedKV:
         self.host, self.nch, self.lens_host = self.host[keep], self.nch[keep], self.lens_host[keep]
         self.nshared = self.nshared[keep]
         self.slot_entry = [self.slot_entry[i] for i in keep.tolist()]
+        self.slot_prefix = [self.slot_prefix[i] for i in keep.tolist()]
         self.B = int(keep.size)
         self.version += 1

@@ -127,42 +127,65 @@ def _multiplicity(contexts, share: bool):
     return keys, [k is not None for k in keys]
 
 
+def _prefix_chains(contexts, on: bool):
+    """One chain of shared prefix runs per message (``kvpages.plan_prefixes`` over the whole call's trimmed contexts:
+    a prefix counts when at least two distinct contexts of the CALL begin with it), or None when prefixes are not
+    shared."""
+    from .kvpages import plan_prefixes
+
+    chains = plan_prefixes(contexts) if on else None
+    return chains if chains is not None and any(chains) else None
+
+
 def _admissible(queue, contexts, check_every: int, nslots: int, room: int, keys=None, shares=None,
-                live=()) -> List[int]:
+                live=(), chains=None, live_prefixes=()) -> List[int]:
     """Pop the messages to admit now from the queue's front: at most ``nslots``, while the pages of their contexts
     and first ``check_every + 1`` positions fit in ``room`` pages (what the pool can still hand out beyond one page
     per live slot).  The admission then maps exactly these pages.  A message that shares its context
     (``shares[m]``, entry key ``keys[m]``) counts its own pages only -- those after the context's full pages -- and
-    its entry's pages once, with the first message of this batch that opens it, unless the entry is ``live``."""
-    from .kvpages import own_pages, shared_pages
+    its entry's pages once, with the first message of this batch that opens it, unless the entry is ``live``.  A
+    message with a chain of shared prefix runs (``chains[m]``) counts the pages after the chain only, and each run's
+    pages once in the same way, unless the run is in ``live_prefixes``; a live entry's chain is live with it."""
+    from .kvpages import chain_past, own_pages, shared_pages
 
-    out, used, opened = [], 0, set()
+    out, used, opened, popened = [], 0, set(), set()
     while queue and len(out) < nslots:
         m = queue[0]
         T = len(contexts[m])
         sh = shares is not None and shares[m]
-        need = own_pages(T, check_every + 1, sh)
+        chain = chains[m] if chains is not None else ()
+        past = chain_past(chain)
+        need = own_pages(T, check_every + 1, sh, past)
         opens = sh and keys[m] not in live and keys[m] not in opened
         if opens:
-            need += shared_pages(T)
+            need += shared_pages(T, past)
+        runs = [k for k, a, b in chain if k not in live_prefixes and k not in popened] if opens or not sh else []
+        need += sum(shared_pages(b, a) for k, a, b in chain if k in runs)
         if used + need > room:
             break
         used += need
         if opens:
             opened.add(keys[m])
+        popened.update(runs)
         out.append(queue.popleft())
     return out
 
 
-def _map_contexts(kv, slots, keys, shares, tl, upto) -> np.ndarray:
+def _map_contexts(kv, slots, keys, shares, tl, upto, chains=None) -> np.ndarray:
     """Page mapping of an admission with per-message contexts: every slot in ``slots`` starts over at its context's
     length ``tl``, a sharing message holds its context's entry (opened here if it is not live), and every message
-    gets its own pages for the positions below ``upto``.  Returns the mask of the slots that were served; the others
-    are left released (the pool is out of memory)."""
+    gets its own pages for the positions below ``upto``.  A message with a chain of shared prefix runs (``chains``,
+    one per slot) holds the chain too -- beneath its context's entry, or itself when only the prefix is shared.
+    Returns the mask of the slots that were served; the others are left released (the pool is out of memory)."""
     kv.reset(slots, lens=tl)
     sh = np.asarray(shares, dtype=bool)
     failed = set()
-    if sh.any():
+    if chains is not None:
+        hd = sh | np.asarray([bool(c) for c in chains], dtype=bool)
+        if hd.any():
+            failed = set(kv.hold(slots[hd], [k if f else None for k, f, h in zip(keys, sh, hd) if h], tl[hd],
+                                 [c for c, h in zip(chains, hd) if h]).tolist())
+    elif sh.any():
         failed = set(kv.hold(slots[sh], [k for k, f in zip(keys, sh) if f], tl[sh]).tolist())
     rest = np.asarray([s not in failed for s in slots.tolist()], dtype=bool)
     failed |= set(kv.ensure(slots[rest], upto[rest]).tolist())
@@ -178,7 +201,8 @@ class SlotEncoder:
     def __init__(self, provider, ctx, bit_lists: Sequence[Sequence[int]], context: Sequence[int], *, slots: int,
                  finish: bool, stop_text: Optional[str], stats: bool, check_every: int, stall_steps: int,
                  hard_cap: int, use_graph: bool, compact: bool = True,
-                 contexts: Optional[Sequence[Sequence[int]]] = None, share: bool = True, qualities=None):
+                 contexts: Optional[Sequence[Sequence[int]]] = None, share: bool = True, qualities=None,
+                 share_prefixes: bool = True):
         self.p, self.lm, self.ctx = provider, provider.lm, ctx
         self.qual = qualities  # coder.StreamQuality with one row per message, or None (the context's one quality)
         self.bits = bit_lists
@@ -190,6 +214,10 @@ class SlotEncoder:
         self.contexts = _trimmed(contexts, self.N) if contexts is not None else None
         # messages of the call with equal contexts share the context's KV pages (lm/kvpages.py)
         self.keys, self.shares = _multiplicity(self.contexts, share) if contexts is not None else (None, None)
+        # different contexts of the call share the pages of a common prefix (fp16 pages only: lm.prefix_sharing)
+        self.chains = _prefix_chains(self.contexts, share and share_prefixes and
+                                     getattr(self.lm, "prefix_sharing", False)) if contexts is not None else None
+        self.prefix_rows_saved = self.prefix_entries = 0
         self.prefill_shared = 0
         self.ctx_len = np.zeros(self.S, dtype=np.int64)  # context rows of the message in each slot (per-context)
         self.prefill_rows = 0
@@ -325,7 +353,7 @@ class SlotEncoder:
                         room = lm.pool.free_pages + lm.pool.growable_pages() - int(live.sum()) - 1
                         if per_ctx:
                             ms = _admissible(queue, self.contexts, self.check_every, empty.size, room, self.keys,
-                                             self.shares, lm.kv.entries)
+                                             self.shares, lm.kv.entries, self.chains, lm.kv.prefixes)
                             if ms:
                                 back = self._admit_contexts(sess, logits, empty[:len(ms)], ms, slot_msg, last_pos,
                                                             last_move, t)
@@ -428,13 +456,17 @@ class SlotEncoder:
         lm = self.lm
         slots = np.asarray(slots, dtype=np.int64)
         tl = np.asarray([len(self.contexts[m]) for m in msgs], dtype=np.int64)
+        chains = [self.chains[m] for m in msgs] if self.chains is not None else None
         ok = _map_contexts(lm.kv, slots, [self.keys[m] for m in msgs], [self.shares[m] for m in msgs], tl,
-                           tl + self.check_every + 1)
+                           tl + self.check_every + 1, chains)
         back = [m for m, k in zip(msgs, ok) if not k]
         slots, msgs = slots[ok], [m for m, k in zip(msgs, ok) if k]
         if not msgs:
             return back
-        first = lm.prefill_contexts([self.contexts[m] for m in msgs], slots, [self.shares[m] for m in msgs])
+        first = lm.prefill_contexts([self.contexts[m] for m in msgs], slots, [self.shares[m] for m in msgs],
+                                    [self.chains[m] for m in msgs] if self.chains is not None else None)
+        self.prefix_rows_saved += lm.last_prefill.get("prefix_rows_saved", 0)
+        self.prefix_entries += lm.last_prefill.get("prefix_entries", 0)
         self.prefill_rows += lm.last_prefill["rows"]
         self.prefill_groups += lm.last_prefill["groups"]
         self.prefill_shared += lm.last_prefill["shared"]
@@ -490,7 +522,8 @@ class SlotDecoder:
 
     def __init__(self, provider, ctx, token_lists: Sequence[Sequence[int]], context: Sequence[int], *, slots: int,
                  use_graph: bool, check_every: int = 16, compact: bool = True,
-                 contexts: Optional[Sequence[Sequence[int]]] = None, share: bool = True, qualities=None):
+                 contexts: Optional[Sequence[Sequence[int]]] = None, share: bool = True, qualities=None,
+                 share_prefixes: bool = True):
         self.p, self.lm, self.ctx = provider, provider.lm, ctx
         self.qual = qualities  # coder.StreamQuality with one row per message, or None
         self.lists = token_lists
@@ -499,6 +532,10 @@ class SlotDecoder:
         self.context = context
         self.contexts = _trimmed(contexts, self.N) if contexts is not None else None  # one per message
         self.keys, self.shares = _multiplicity(self.contexts, share) if contexts is not None else (None, None)
+        # different contexts of the call share the pages of a common prefix (fp16 pages only: lm.prefix_sharing)
+        self.chains = _prefix_chains(self.contexts, share and share_prefixes and
+                                     getattr(self.lm, "prefix_sharing", False)) if contexts is not None else None
+        self.prefix_rows_saved = self.prefix_entries = 0
         self.prefill_shared = 0
         self.prefill_rows = 0
         self.prefill_groups = 0
@@ -617,7 +654,8 @@ class SlotDecoder:
                         room = lm.pool.free_pages + lm.pool.growable_pages() - int(live.sum()) - 1
                         if per_ctx:
                             adm_m = _admissible(queue, self.contexts, self.check_every, empty.size, room,
-                                                self.keys, self.shares, lm.kv.entries)
+                                                self.keys, self.shares, lm.kv.entries, self.chains,
+                                                lm.kv.prefixes)
                             if adm_m:
                                 back = self._admit_contexts(st, logits, init_row, empty[:len(adm_m)], adm_m, slot_msg,
                                                             nlen_host, ctx_host, Tcap)
@@ -708,13 +746,17 @@ class SlotDecoder:
         slots = np.asarray(slots, dtype=np.int64)
         tl = np.asarray([len(self.contexts[m]) for m in msgs], dtype=np.int64)
         nl = np.asarray([len(self.lists[m]) for m in msgs], dtype=np.int64)
+        chains = [self.chains[m] for m in msgs] if self.chains is not None else None
         ok = _map_contexts(lm.kv, slots, [self.keys[m] for m in msgs], [self.shares[m] for m in msgs], tl,
-                           tl + np.minimum(self.check_every + 1, nl))
+                           tl + np.minimum(self.check_every + 1, nl), chains)
         back = [m for m, k in zip(msgs, ok) if not k]
         slots, msgs, tl = slots[ok], [m for m, k in zip(msgs, ok) if k], tl[ok]
         if not msgs:
             return back
-        first = lm.prefill_contexts([self.contexts[m] for m in msgs], slots, [self.shares[m] for m in msgs])
+        first = lm.prefill_contexts([self.contexts[m] for m in msgs], slots, [self.shares[m] for m in msgs],
+                                    [self.chains[m] for m in msgs] if self.chains is not None else None)
+        self.prefix_rows_saved += lm.last_prefill.get("prefix_rows_saved", 0)
+        self.prefix_entries += lm.last_prefill.get("prefix_entries", 0)
         self.prefill_rows += lm.last_prefill["rows"]
         self.prefill_groups += lm.last_prefill["groups"]
         self.prefill_shared += lm.last_prefill["shared"]
