@@ -26,6 +26,23 @@ extern "C" {
 int ns_score_rows(const void* d_logits, int64_t ld, int64_t nrows, int V, int dtype, const int32_t* d_labels,
                   double* d_nll, double* d_entropy, void* hip_stream);
 
+/* The head GEMM with the row scores as its epilogue: nll / entropy of the rows of softmax(x @ wt^T) without a
+ * [M, V] logits array.  d_x: fp16 [M, K] (the ln_f rows), d_wt: fp16 [V, K] (K contiguous, as ns_lm_gemm takes it),
+ * both 16-byte aligned with ldx, ldw multiples of 8.  The logit of (row, column) has the bits ns_lm_gemm stores with
+ * NS_LM_EPI_STORE_F32 (one canonical MFMA chain); with logits_dtype == NS_DTYPE_F16 it is rounded to fp16 and widened
+ * back first, as NS_LM_EPI_STORE followed by ns_score_rows sees it.  d_labels / d_nll / d_entropy as in ns_score_rows
+ * (a label < 0 or >= V gives nll 0).  A workgroup reduces 128 rows over a span of column tiles into one fp32
+ * (max, sum e, sum e x) per (row, span) in d_work; a second kernel merges a row's spans in ascending order in float64.
+ * The span cut and every reduction order depend on V only: a row's outputs have the same bits at M = 1 and inside any
+ * batch.  d_work: 16-byte aligned, at least ns_lm_head_score_work_bytes(M, V) bytes (contents are scratch).
+ * Returns NS_ERR_CONFIG for a NULL d_x / d_wt / d_work, a misaligned pointer or stride or a short d_work; NS_OK
+ * without a launch for M == 0 or both outputs NULL; NS_ERR_UNSUPPORTED for a K of more than one accumulator chain
+ * (K > 1024) or no multiple of 64 -- the caller then runs ns_lm_gemm + ns_score_rows. */
+int ns_lm_head_score(const void* d_x, int64_t ldx, const void* d_wt, int64_t ldw, int M, int V, int K,
+                     int logits_dtype, const int32_t* d_labels, double* d_nll, double* d_entropy, void* d_work,
+                     int64_t work_bytes, void* hip_stream);
+int64_t ns_lm_head_score_work_bytes(int M, int V);
+
 #ifdef __cplusplus
 }
 #endif

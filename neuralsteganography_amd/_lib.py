@@ -32,7 +32,8 @@ EXPORTS = ("ns_create", "ns_destroy", "ns_last_error", "ns_version", "ns_max_top
            "ns_stream_quality_fill", "ns_set_stream_quality",
            "ns_read_counters", "ns_decode_attention", "ns_decode_attention_dev", "ns_decode_attention_prefix",
            "ns_decode_attention_fp8", "ns_decode_attention_ex", "ns_quantize_fp8",
-           "ns_score_rows", "ns_lm_gemm", "ns_lm_gemm_config", "ns_lm_gemm_configs", "ns_lm_layernorm",
+           "ns_score_rows", "ns_lm_head_score", "ns_lm_head_score_work_bytes",
+           "ns_lm_gemm", "ns_lm_gemm_config", "ns_lm_gemm_configs", "ns_lm_layernorm",
            "ns_lm_layernorm_count",
            "ns_lm_embed_ln", "ns_lm_embed_seq_ln", "ns_seq_attention", "ns_lm_ln_gemm",
            "ns_decode_attention_paged", "ns_lm_embed_ln_rows", "ns_lm_layernorm_rows", "ns_seq_attention_ragged",
@@ -144,6 +145,11 @@ def lib() -> ctypes.CDLL:
     L.ns_read_counters.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.ns_score_rows.restype = ctypes.c_int
     L.ns_score_rows.argtypes = [vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
+    L.ns_lm_head_score.restype = ctypes.c_int
+    L.ns_lm_head_score.argtypes = [vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                   ctypes.c_int, vp, vp, vp, vp, ctypes.c_int64, vp]
+    L.ns_lm_head_score_work_bytes.restype = ctypes.c_int64
+    L.ns_lm_head_score_work_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
     L.ns_decode_attention_dev.restype = ctypes.c_int
     L.ns_decode_attention_dev.argtypes = [vp, ctypes.c_int64, vp, vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                           ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int64,

@@ -10,7 +10,9 @@ overrides), guard (``QualityGuard(LMScorer(prefer_transformers=False))`` by defa
 ``cover_generate_batch`` runs the same schedule for MANY secrets: attempt r encodes every still-rejected
 secret in ONE lockstep batch (all their packets are streams of one GPT-2 + HIP-coder loop,
 ``stego_encode_batch``), the guard scores all the resulting covers at once (one batched GPU forward on the
-transformers branch), and only the rejected secrets go on to attempt r+1.
+transformers branch), and only the rejected secrets go on to attempt r+1.  With ``seed_texts`` every secret has
+its own seed (one conversation per recipient) and follows that seed's schedule; ``cover_reveal_batch`` and
+``texts_to_spans`` take ``seed_texts`` likewise.
 """
 
 from __future__ import annotations
@@ -151,49 +153,92 @@ def _ensure_cover_lm(lm):
         raise ConfigurationError("failed to load default language model") from exc
 
 
-def _render_covers(payloads: Sequence[bytes], *, seed_text: str, quality: Mapping[str, Any], chunk_bytes: int,
+def _one_or_many_seeds(seed_text: Optional[str], seed_texts: Optional[Sequence[str]], n: int):
+    """``(seed_text, None)`` for a shared seed, ``(None, seeds)`` for one seed per message (``n`` of them).  Exactly
+    one of the two must be given."""
+    if (seed_text is None) == (seed_texts is None):
+        raise ConfigurationError("give exactly one of seed_text (shared) and seed_texts (one per message)")
+    if seed_texts is None:
+        return seed_text, None
+    seeds = [str(s) for s in seed_texts]
+    if len(seeds) != n:
+        raise ConfigurationError(f"{len(seeds)} seed texts for {n} messages")
+    return None, seeds
+
+
+def _render_covers(payloads: Sequence[bytes], *, seed_text: Optional[str] = None,
+                   seed_texts: Optional[Sequence[str]] = None, quality: Mapping[str, Any], chunk_bytes: int,
                    use_crc: bool, ecc: str, nsym: int, lm) -> List[str]:
-    """``_generate_cover_once`` (``api.py:526-562``) for many payloads: one batched stego_encode."""
+    """``_generate_cover_once`` (``api.py:526-562``) for many payloads: one batched stego_encode.  ``seed_texts``:
+    one seed per payload (equal seeds are passed on as one shared ``seed_text``), each cover rendered after its own
+    seed's ids."""
+    seeds = [seed_text] * len(payloads) if seed_texts is None else list(seed_texts)
+    skw = {"seed_texts": seeds} if len(set(seeds)) > 1 else {"seed_text": seeds[0] if seeds else (seed_text or "")}
     results = stego_encode_batch(list(payloads), chunk_bytes=chunk_bytes, use_crc=use_crc, ecc=ecc, nsym=nsym,
-                                 quality=dict(quality), seed_text=seed_text, lm=lm)
+                                 quality=dict(quality), lm=lm, **skw)
     tok = _tokenizer_of(lm)
-    seed_ids = seed_to_ids(seed_text, tok)
-    return [spans_to_text([list(map(int, s)) for s in res], seed_ids, tok) for res in results]
+    ids = {s: seed_to_ids(s, tok) for s in set(seeds)}
+    return [spans_to_text([list(map(int, s)) for s in res], ids[seed], tok) for res, seed in zip(results, seeds)]
 
 
-def cover_generate_batch(secrets: Sequence[Any], *, seed_text: str, quality: Optional[Mapping[str, object]] = None,
+def cover_generate_batch(secrets: Sequence[Any], *, seed_text: Optional[str] = None,
+                         seed_texts: Optional[Sequence[str]] = None,
+                         quality: Optional[Mapping[str, object]] = None,
                          chunk_bytes: int = 256, use_crc: bool = True, ecc: str = "rs", nsym: int = 10, lm=None,
                          quality_gate: bool = True, gate_thresholds: Optional[Mapping[str, float]] = None,
                          regen_attempts: int = 2, regen_strategy: Optional[Mapping[str, Any]] = None,
-                         quality_guard: Optional[QualityGuard] = None, return_errors: bool = False) -> List[Any]:
+                         quality_guard: Optional[QualityGuard] = None, return_errors: bool = False,
+                         return_attempts: bool = False) -> List[Any]:
     """One cover text per secret.  A secret whose every attempt is rejected raises ``QualityGateError`` (the
-    first such, in input order), or leaves the error in its slot with ``return_errors=True``."""
+    first such, in input order), or leaves the error in its slot with ``return_errors=True``.
+
+    Exactly one of ``seed_text`` (shared) and ``seed_texts`` (one per secret, as each ``cover_generate`` call of the
+    reference has its own seed, e.g. one conversation per recipient) is given.  Message ``i`` then follows the
+    schedule of ITS seed, ``iter_attempts(seed_texts[i], ...)``: attempt 1 uses its own seed, later attempts the
+    pool's seeds (equal across messages: one shared context) and, once the pool is empty, its own seed again.
+    Attempt r is still one ``stego_encode_batch`` over the still-rejected messages and one ``evaluate_batch``; the
+    results equal ``cover_generate(secrets[i], seed_text=seed_texts[i], ...)`` one at a time.
+
+    ``return_attempts``: a passed slot holds ``(text, Attempt)`` -- the receiver needs the seed of the attempt that
+    was accepted (``Attempt.seed_text``; ``seed_variant`` is ``"base"`` or ``"alt-<r>"``)."""
     payloads = [_normalise_secret(s) for s in secrets]
+    n = len(payloads)
+    seed_text, seeds = _one_or_many_seeds(seed_text, seed_texts, n)
+    if seeds is None:
+        seeds = [seed_text] * n
     provider = _ensure_cover_lm(lm)
     q = normalise_quality(quality)
     kw = dict(chunk_bytes=chunk_bytes, use_crc=use_crc, ecc=ecc, nsym=nsym, lm=provider)
     if not quality_gate:
-        return _render_covers(payloads, seed_text=seed_text, quality=q, **kw)
+        texts = _render_covers(payloads, seed_texts=seeds, quality=q, **kw)
+        if return_attempts:
+            return [(t, Attempt(s, {}, "base")) for t, s in zip(texts, seeds)]
+        return texts
     thresholds = prepare_gate_thresholds(gate_thresholds)
     guard = _ensure_guard(quality_guard)
     total = max(regen_attempts, 0) + 1
-    out: List[Any] = [None] * len(payloads)
+    out: List[Any] = [None] * n
     last: Dict[int, tuple] = {}
-    pending = list(range(len(payloads)))
-    for idx, att in enumerate(iter_attempts(seed_text, regen_attempts, regen_strategy or {}), start=1):
+    pending = list(range(n))
+    # one schedule per distinct seed: the seeds differ per message, the overrides and variants per attempt do not
+    schedules = {s: list(iter_attempts(s, regen_attempts, regen_strategy or {})) for s in set(seeds)}
+    common = list(iter_attempts("", regen_attempts, regen_strategy or {}))
+    for idx, att in enumerate(common, start=1):
         if not pending:
             break
         aq = dict(q)
         aq.update(att.overrides)
-        texts = _render_covers([payloads[i] for i in pending], seed_text=att.seed_text, quality=aq, **kw)
+        atts = [schedules[seeds[i]][idx - 1] for i in pending]
+        texts = _render_covers([payloads[i] for i in pending], seed_texts=[a.seed_text for a in atts], quality=aq,
+                               **kw)
         verdicts: List[GuardResult] = guard.evaluate_batch(texts, thresholds)
         rejected = []
-        for i, text, v in zip(pending, texts, verdicts):
+        for i, text, v, a in zip(pending, texts, verdicts, atts):
             status = "PASS" if v.passed else "REJECT"
             log.info("quality attempt %d/%d (%s) message %d -> %s %s", idx, total, att.seed_variant, i, status,
                      "; ".join(v.reasons))
             if v.passed:
-                out[i] = text
+                out[i] = (text, a) if return_attempts else text
             else:
                 last[i] = (text, v)
                 rejected.append(i)
@@ -291,35 +336,53 @@ def _cover_ids(text: str, seed_text: str, seed_ids: List[int], tok) -> Optional[
     return None
 
 
-def texts_to_spans(texts: Sequence[str], *, seed_text: str, lm, quality: Optional[Mapping[str, object]] = None
-                   ) -> List[List[List[int]]]:
+def texts_to_spans(texts: Sequence[str], *, seed_text: Optional[str] = None,
+                   seed_texts: Optional[Sequence[str]] = None, lm,
+                   quality: Optional[Mapping[str, object]] = None) -> List[List[List[int]]]:
     """Recover the token spans of many cover texts (the inverse of ``spans_to_text``, which the reference leaves
     unimplemented, ``codec/textio.py:58-63``).  The text is re-tokenised, the seed's ids are stripped, and the
     spans are found one per round: every cover's next span is decoded as one stream of a lockstep batch, the
     packet completes at a known token and the span ends there or, with ``finish_sent``, at the following
     sentence end.  A text that re-tokenises differently from the emitted ids (GPT-2 BPE merges, also across
     span boundaries) is repaired while decoding with the reference's heuristics (``code_base/arithmetic.py:
-    233-242,300-342``, the provider's ``decode_counted_repair``): the spans are the repaired ids."""
+    233-242,300-342``, the provider's ``decode_counted_repair``): the spans are the repaired ids.
+
+    Exactly one of ``seed_text`` (shared) and ``seed_texts`` (one per text) is given.  With ``seed_texts`` every
+    text is stripped of its own seed and decoded after its own context: one lockstep batch with one context per
+    stream on a provider whose counted decodes take ``contexts=``, one batch per distinct context otherwise."""
     from .codec.errors import DecodeDivergenceError
     from .lm.mock import MockLM
-    from .stego import _quality_args
+    from .stego import _quality_args, _takes_contexts
 
     tok = _tokenizer_of(lm)
-    seed_ids = seed_to_ids(seed_text, tok)
+    seed_text, seeds = _one_or_many_seeds(seed_text, seed_texts, len(texts))
+    if seeds is None:
+        seeds = [seed_text] * len(texts)
+    seed_ids = {s: seed_to_ids(s, tok) for s in set(seeds)}
+    contexts = {s: list(lm.encode_seed(s)) for s in set(seeds)}
     q = _quality_args(quality)
     finish = bool(q.get("finish_sent")) and hasattr(lm, "sentence_end_table")
     sent_end = lm.sentence_end_table() if finish else None
     rest: List[List[int]] = []
     for i, text in enumerate(texts):
-        ids = _cover_ids(text, seed_text, seed_ids, tok)
+        ids = _cover_ids(text, seeds[i], seed_ids[seeds[i]], tok)
         if ids is None:
             raise DecodeDivergenceError(f"cover {i} does not start with the seed text")
         rest.append(_split_double_newlines(ids, tok))
-    context = list(lm.encode_seed(seed_text))
-    spans: List[List[List[int]]] = [[] for _ in texts]
-    active = [i for i in range(len(texts)) if rest[i]]
-    while active:
-        lists = [rest[i] for i in active]
+    if hasattr(lm, "decode_counted_repair"):
+        entry = lm.decode_counted_repair
+    elif hasattr(lm, "decode_counted"):
+        entry = lm.decode_counted
+    elif isinstance(lm, MockLM):
+        entry = None
+    else:
+        raise NotImplementedError("text_to_spans needs a provider with decode_counted (or the mock)")
+
+    def decode_round(members: List[int], context=None, per_stream=None):
+        """One lockstep decode of the next span of ``members``, after the shared ``context`` or one context per
+        stream: (bits, counts, lists, edits, originals)."""
+        lists = [rest[i] for i in members]
+        args, ckw = ((context,), {}) if per_stream is None else ((), {"contexts": per_stream})
 
         def settled(bits_l, counts_l, toks_l=None):
             toks_l = lists if toks_l is None else toks_l
@@ -327,17 +390,32 @@ def texts_to_spans(texts: Sequence[str], *, seed_text: str, lm, quality: Optiona
 
         edits_l = [[] for _ in lists]
         orig = [list(l) for l in lists]
-        if hasattr(lm, "decode_counted_repair"):
-            bits_l, counts_l, lists, edits_l = lm.decode_counted_repair(lists, context, quality=q, done=settled)
-        elif hasattr(lm, "decode_counted"):
-            bits_l, counts_l = lm.decode_counted(lists, context, quality=q, done=settled)
-        elif isinstance(lm, MockLM):  # identity coder: 8 bits per token
+        if entry is None:  # the mock's identity coder: 8 bits per token
             bits_l = [lm.decode_arithmetic(l, context, quality=q) for l in lists]
             counts_l = [[8 * (t + 1) for t in range(len(l))] for l in lists]
+        elif hasattr(lm, "decode_counted_repair"):
+            bits_l, counts_l, lists, edits_l = entry(lists, *args, quality=q, done=settled, **ckw)
         else:
-            raise NotImplementedError("text_to_spans needs a provider with decode_counted (or the mock)")
+            bits_l, counts_l = entry(lists, *args, quality=q, done=settled, **ckw)
+        return bits_l, counts_l, lists, edits_l, orig
+
+    spans: List[List[List[int]]] = [[] for _ in texts]
+    active = [i for i in range(len(texts)) if rest[i]]
+    while active:
+        distinct = list(dict.fromkeys(seeds[i] for i in active))
+        if len(distinct) == 1:
+            runs = [(active, {"context": contexts[distinct[0]]})]
+        elif entry is not None and _takes_contexts(entry):
+            runs = [(active, {"per_stream": [contexts[seeds[i]] for i in active]})]
+        else:  # one lockstep batch per distinct context
+            runs = [([i for i in active if seeds[i] == s], {"context": contexts[s]}) for s in distinct]
+        ends: Dict[int, tuple] = {}
+        for members, ckw in runs:
+            for i, b, c, l, ed, o in zip(members, *decode_round(members, **ckw)):
+                ends[i] = (b, c, l, ed, o)
         nxt = []
-        for i, l, b, c, ed, o in zip(active, lists, bits_l, counts_l, edits_l, orig):
+        for i in active:
+            b, c, l, ed, o = ends[i]
             end = _span_end(b, c, l, finish, sent_end)
             if end is None:
                 raise DecodeDivergenceError(f"cover {i}: no complete packet in the remaining {len(l)} tokens")
@@ -361,13 +439,16 @@ def _looks_like_spans_json(text: str) -> bool:
         return False
 
 
-def cover_reveal_batch(cover_texts: Sequence[str], *, seed_text: str, quality: Optional[Mapping[str, object]] = None,
+def cover_reveal_batch(cover_texts: Sequence[str], *, seed_text: Optional[str] = None,
+                       seed_texts: Optional[Sequence[str]] = None, quality: Optional[Mapping[str, object]] = None,
                        use_crc: bool = True, ecc: str = "rs", nsym: int = 10, lm=None,
                        return_errors: bool = False) -> List[Any]:
     """:func:`cover_reveal` for many covers: spans of all texts recovered round by round in lockstep batches,
-    then one batched ``stego_decode``."""
+    then one batched ``stego_decode``.  Exactly one of ``seed_text`` (shared) and ``seed_texts`` (one per cover: the
+    seed of the attempt that produced it, ``cover_generate_batch(..., return_attempts=True)``) is given."""
     from .stego import stego_decode_batch
 
+    seed_text, seeds = _one_or_many_seeds(seed_text, seed_texts, len(cover_texts))
     provider = _ensure_cover_lm(lm)
     q = normalise_quality(quality)
     span_sets: List[Any] = [None] * len(cover_texts)
@@ -378,11 +459,12 @@ def cover_reveal_batch(cover_texts: Sequence[str], *, seed_text: str, quality: O
         else:
             plain.append(i)
     if plain:
-        for i, sp in zip(plain, texts_to_spans([cover_texts[i] for i in plain], seed_text=seed_text, lm=provider,
-                                                quality=q)):
+        skw = {"seed_text": seed_text} if seeds is None else {"seed_texts": [seeds[i] for i in plain]}
+        for i, sp in zip(plain, texts_to_spans([cover_texts[i] for i in plain], lm=provider, quality=q, **skw)):
             span_sets[i] = sp
-    return stego_decode_batch(span_sets, use_crc=use_crc, ecc=ecc, nsym=nsym, quality=q, seed_text=seed_text,
-                              lm=provider, return_errors=return_errors)
+    skw = {"seed_text": seed_text} if seeds is None else {"seed_texts": seeds}
+    return stego_decode_batch(span_sets, use_crc=use_crc, ecc=ecc, nsym=nsym, quality=q, lm=provider,
+                              return_errors=return_errors, **skw)
 
 
 def cover_reveal(cover_text: str, *, seed_text: str, quality: Optional[Mapping[str, object]] = None,

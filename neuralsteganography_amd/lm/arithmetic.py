@@ -555,21 +555,33 @@ class HipArithmeticLM:
             return (qs[0] if qs else {}), None
         return None, plist
 
-    def decode_counted(self, token_lists: Sequence[Sequence[int]], context: Sequence[int], *,
-                       quality: Mapping[str, object], done=None, check_every: int = 64):
+    def decode_counted(self, token_lists: Sequence[Sequence[int]], context: Optional[Sequence[int]] = None, *,
+                       contexts: Optional[Sequence[Sequence[int]]] = None, quality: Mapping[str, object], done=None,
+                       check_every: int = 64):
         """``decode_batch`` that also records, per stream, the cumulative number of bits emitted after each
         token (the span splitter of ``text_to_spans`` needs the token at which a packet completes).  A stream
         whose token falls outside the kept top-k stops emitting (its later counts stay flat) instead of
         raising.  ``done(bits_lists, counts_lists) -> bool`` is polled every ``check_every`` tokens and ends
-        the loop early once it holds.  Returns ``(bits per stream, counts per stream)``."""
+        the loop early once it holds.  Returns ``(bits per stream, counts per stream)``.
+
+        Exactly one of ``context`` (shared) and ``contexts`` (one per stream, as in :meth:`decode_batch`) is given.
+        With ``contexts`` the native model prefills every stream's own context into its KV pages
+        (``BatchedGPT2.prefill_contexts``: equal contexts and common prefixes share pages) and the same lockstep
+        loop runs; a stream's bits and counts equal those of the stream run alone with ``context=``.  A non-native
+        LM runs the loop once per distinct context (``done`` then sees that context's streams only), results in the
+        caller's order."""
         import numpy as np
         import torch
 
         from ..coder import _state_fields
 
         B = len(token_lists)
+        context, contexts = _one_or_many(context, contexts, B)
         if B == 0:
             return [], []
+        if contexts is not None and not getattr(self.lm, "native", False):
+            return self._counted_by_context(self.decode_counted, token_lists, contexts, 2, quality=quality,
+                                            done=done, check_every=check_every)
         for tl in token_lists:
             if any((int(t) < 0 or int(t) >= self.vocab) for t in tl):
                 from ..codec.errors import DecodeDivergenceError
@@ -579,7 +591,7 @@ class HipArithmeticLM:
         ctx = self._coder(params, B)
         sess = DecodeSession(ctx, token_lists)
         counts = torch.zeros((max(sess.T, 1), B), dtype=torch.int64, device=sess.state.device)
-        logits = self.lm.prefill(context, B, max(sess.T, 1) + 1)
+        logits = self._prefill_streams(context, contexts, B, max(sess.T, 1) + 1)
 
         def snapshot(n):
             f = _state_fields(sess.state)
@@ -607,16 +619,49 @@ class HipArithmeticLM:
             return self.lm.step(tokens, live=live)
         return self.lm.step(tokens)
 
-    def decode_tokens_repair(self, token_lists: Sequence[Sequence[int]], context: Sequence[int], *,
+    def _prefill_streams(self, context, contexts, B: int, max_new: int):
+        """First logits ``[B, ld]`` of the lockstep decodes: the shared ``context`` broadcast to ``B`` streams, or
+        (native model) ``contexts[b]`` prefilled into stream ``b``'s own KV pages."""
+        if contexts is None:
+            return self.lm.prefill(context, B, max_new)
+        import numpy as np
+
+        self.lm.begin_slots(B, 0, max_new)
+        kw = {}
+        if not self.share_contexts:
+            kw["shared"] = [False] * B
+        elif not self.share_prefixes:
+            kw["chains"] = [()] * B
+        return self.lm.prefill_contexts(contexts, np.arange(B), **kw)
+
+    def _counted_by_context(self, entry, token_lists, contexts, nres: int, **kw):
+        """Non-native LMs: ``entry`` (a counted decode, returning ``nres`` per-stream lists) once per distinct
+        context over that context's streams, results back in the caller's order (as :meth:`_by_context`)."""
+        groups: Dict[tuple, List[int]] = {}
+        for i, c in enumerate(contexts):
+            groups.setdefault(tuple(c), []).append(i)
+        out = [[None] * len(token_lists) for _ in range(nres)]
+        for c, members in groups.items():
+            res = entry([token_lists[i] for i in members], list(c), **kw)
+            for k in range(nres):
+                for j, i in enumerate(members):
+                    out[k][i] = res[k][j]
+        return tuple(out)
+
+    def decode_tokens_repair(self, token_lists: Sequence[Sequence[int]], context: Optional[Sequence[int]] = None, *,
+                             contexts: Optional[Sequence[Sequence[int]]] = None,
                              quality: Mapping[str, object], enc=None) -> List[List[int]]:
         """Batched ``decode_arithmetic`` token loop with the reference's BPE repair (code_base/arithmetic.py
         :254-371): a received token outside the kept top-k' is repaired on the host from the kernel's
         ranked ids (:300-342, :func:`bpe_repair`), the token list is edited as the reference edits it, and
         the step is re-issued; an unrepairable token decodes as rank 0 while the LM is still fed the
-        received token, exactly as the reference does.  Returns every emitted bit per stream."""
-        return self.decode_counted_repair(token_lists, context, quality=quality, enc=enc, strict=True)[0]
+        received token, exactly as the reference does.  Returns every emitted bit per stream.  ``context`` /
+        ``contexts`` as in :meth:`decode_counted`."""
+        return self.decode_counted_repair(token_lists, context, contexts=contexts, quality=quality, enc=enc,
+                                          strict=True)[0]
 
-    def decode_counted_repair(self, token_lists: Sequence[Sequence[int]], context: Sequence[int], *,
+    def decode_counted_repair(self, token_lists: Sequence[Sequence[int]], context: Optional[Sequence[int]] = None, *,
+                              contexts: Optional[Sequence[Sequence[int]]] = None,
                               quality: Mapping[str, object], enc=None, done=None, check_every: int = 64,
                               strict: bool = False):
         """:meth:`decode_tokens_repair` that also returns, per stream, the cumulative number of bits emitted
@@ -628,7 +673,9 @@ class HipArithmeticLM:
         Returns ``(bits per stream, counts per stream, token lists, edits)``: ``edits[b]`` lists ``(p, list)``,
         the stream's token list after each repair at position ``p`` (a repair at ``p`` changes positions >= p
         only), so a caller that learns afterwards that the stream ended at token e takes the list of the last
-        repair at p <= e -- tokens decoded past e (another span's, out of context) may have been "repaired"."""
+        repair at p <= e -- tokens decoded past e (another span's, out of context) may have been "repaired".
+        ``context`` / ``contexts`` as in :meth:`decode_counted`: with one context per stream, a stream's bits, counts,
+        repaired list and edits equal those of the stream run alone with ``context=``."""
         import torch
 
         from ..coder import _state_fields
@@ -636,15 +683,19 @@ class HipArithmeticLM:
         enc = enc if enc is not None else self.tokenizer
         lists = [[int(t) for t in tl] for tl in token_lists]
         B = len(lists)
+        context, contexts = _one_or_many(context, contexts, B)
         if B == 0:
             return [], [], [], []
+        if contexts is not None and not getattr(self.lm, "native", False):
+            return self._counted_by_context(self.decode_counted_repair, lists, contexts, 4, quality=quality, enc=enc,
+                                            done=done, check_every=check_every, strict=strict)
         for tl in lists:  # received ids feed the embedding gather: validate on the host first
             if any(not 0 <= t < self.vocab for t in tl):
                 raise ConfigurationError(f"received token id outside [0, {self.vocab})")
         params = coder_params_from_quality(quality, self.vocab, self.logits_dtype, self.banned)
         ctx = self._coder(params, B)
         sess = StreamingDecodeSession(ctx, B, max_tokens=max(len(x) for x in lists) + 8)
-        logits = self.lm.prefill(context, B, max(len(x) for x in lists) + 8)
+        logits = self._prefill_streams(context, contexts, B, max(len(x) for x in lists) + 8)
         pos = [0] * B
         counts: List[List[int]] = [[] for _ in range(B)]
         edits: List[list] = [[] for _ in range(B)]

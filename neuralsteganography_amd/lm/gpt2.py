@@ -681,6 +681,96 @@ class BatchedGPT2:
         return out
 
     @torch.no_grad()
+    def forward_packed(self, seqs: Sequence[Sequence[int]]):
+        """Causal forward of whole sequences packed back to back, positions ``0..len-1`` each and no cache (the
+        guard's scoring pass without padding rows; native path only): the embedding at each row's own position, the
+        layer GEMMs over the ``R = sum(len)`` packed rows and ``ns_seq_attention_ragged`` in its attention-only mode
+        (NULL page table: no KV page is touched).  Returns ``(h, seq_start)``: the ``[R, C]`` residual rows before
+        ln_f and the int32 ``[n + 1]`` row starts.  Every kernel is row-wise or per sequence, so a sequence's rows
+        have the bits :meth:`forward_sequences` gives them in any padded batch."""
+        if not self.native:
+            raise RuntimeError("forward_packed needs the native HIP path (fp16 on the GPU)")
+        from .. import _lib
+        from ..coder import _stream_handle
+
+        s = self.shape
+        C, H = s.n_embd, s.n_head
+        D = C // H
+        L = _lib.lib()
+        st = _stream_handle()
+        dev = self.device
+        seqs = [[int(t) for t in q] for q in seqs]
+        for q in seqs:
+            if len(q) < 1:
+                raise ValueError("every sequence needs at least one token")
+            if len(q) > s.n_positions:
+                raise ValueError(f"sequence longer than n_positions ({s.n_positions})")
+            if min(q) < 0 or max(q) >= s.vocab:  # host check: never gather out of the table
+                raise ValueError(f"token ids must lie in [0, {s.vocab})")
+        lens = [len(q) for q in seqs]
+        seq_start, blocks = ragged_blocks(lens)
+        R, n = int(seq_start[-1]), len(seqs)
+        tok = torch.from_numpy(np.concatenate([np.asarray(q, dtype=np.int32) for q in seqs])).to(dev)
+        pos = torch.from_numpy(np.concatenate([np.arange(t, dtype=np.int32) for t in lens])).to(dev)
+        d_start = torch.from_numpy(seq_start).to(dev)
+        d_blocks = torch.from_numpy(blocks).to(dev)
+
+        def embed(h, a, lw0, eps):
+            _check(L.ns_lm_embed_ln_rows(tok.data_ptr(), self.wte.data_ptr(), self.wpe.data_ptr(), s.vocab,
+                                         s.n_positions, pos.data_ptr(), h.data_ptr(), C, lw0["ln1_w"].data_ptr(),
+                                         lw0["ln1_b"].data_ptr(), a.data_ptr(), C, R, C, eps, st),
+                   "ns_lm_embed_ln_rows")
+
+        def attention(i, qkv, o):
+            _check(L.ns_seq_attention_ragged(qkv.data_ptr(), qkv.stride(0), o.data_ptr(), o.stride(0),
+                                             d_start.data_ptr(), n, R, d_blocks.data_ptr(), blocks.shape[0], H, D,
+                                             1.0 / math.sqrt(D), None, 0, 0, None, 0, 0, self._kv_format, st),
+                   "ns_seq_attention_ragged")
+
+        return self._rows_native(R, embed, attention), seq_start
+
+    @torch.no_grad()
+    def score_packed(self, seqs: Sequence[Sequence[int]], fused: bool = False):
+        """Per-row scores of packed sequences: ``(nll, ent, seq_start)`` -- float64 device tensors ``[R]`` over the
+        rows of :meth:`forward_packed`; row ``t`` of a sequence has label ``ids[t + 1]``, its last row label -1
+        (``nll`` 0).  ``fused``: ln_f, then ``ns_lm_head_score`` (the head GEMM with the scores as its epilogue: no
+        ``[R, V]`` logits array; the order of the softmax sums differs from ``ns_score_rows``, so the last bits do);
+        where that kernel does not take the shape (``NS_ERR_UNSUPPORTED``: a K of more than one chain), and with
+        ``fused`` off, the head GEMM into ``[R, ld]`` logits followed by ``ns_score_rows``."""
+        from .. import _lib
+        from ..coder import _stream_handle
+
+        L = _lib.lib()
+        st = _stream_handle()
+        s = self.shape
+        C, V, dev = s.n_embd, s.vocab, self.device
+        h, seq_start = self.forward_packed(seqs)
+        R = h.shape[0]
+        labels = np.full(R, -1, dtype=np.int32)
+        for q, a in zip(seqs, seq_start[:-1]):
+            labels[a: a + len(q) - 1] = np.asarray(q[1:], dtype=np.int32)
+        lab = torch.from_numpy(labels).to(dev)
+        nll = torch.empty(R, dtype=torch.float64, device=dev)
+        ent = torch.empty_like(nll)
+        dt = _lib.NS_DTYPE_F16 if self.logits_dtype == torch.float16 else _lib.NS_DTYPE_F32
+        if fused:
+            a = torch.empty_like(h)
+            _check(L.ns_lm_layernorm(h.data_ptr(), C, self.lnf_w.data_ptr(), self.lnf_b.data_ptr(), a.data_ptr(), C,
+                                     R, C, float(s.eps), st), "ns_lm_layernorm")
+            nbytes = int(L.ns_lm_head_score_work_bytes(R, V))
+            work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            rc = L.ns_lm_head_score(a.data_ptr(), C, self.head_t.data_ptr(), self.head_t.stride(0), R, V, C, dt,
+                                    lab.data_ptr(), nll.data_ptr(), ent.data_ptr(), work.data_ptr(), nbytes, st)
+            if rc == 0:
+                return nll, ent, seq_start
+            if rc != _lib.NS_ERR_UNSUPPORTED:
+                raise RuntimeError(f"ns_lm_head_score failed ({rc})")
+        rows = self._head_native(h)
+        _check(L.ns_score_rows(rows.data_ptr(), rows.stride(0), R, V, dt, lab.data_ptr(), nll.data_ptr(),
+                               ent.data_ptr(), st), "ns_score_rows")
+        return nll, ent, seq_start
+
+    @torch.no_grad()
     def window_logits(self, ids: torch.Tensor) -> torch.Tensor:
         """Next-token logits ``[B, ld]`` of B token windows ``[B, W]`` each run from scratch with positions
         0..W-1 -- the src provider's ``_ModelAdapter`` forward over a context trimmed to ``max_context``

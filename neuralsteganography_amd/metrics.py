@@ -6,8 +6,9 @@
   with ``prefer_transformers=False`` (the api's default guard, ``api.py:118-127``) the deterministic
   fallback -- an empirical unigram model of the text's own whitespace tokens; otherwise a GPU scorer.
 * :class:`HipLMScorer`: the transformers branch for many texts at once -- one causal GPT-2 forward over the
-  padded batch (PyTorch-ROCm GEMMs) and the HIP row kernel ``ns_score_rows`` (``include/nsg_score.h``), which
-  streams each position's logits once for the label's NLL and the row entropy.  ``ppl = exp(mean NLL)``
+  texts (packed back to back on the native model, padded otherwise) and the HIP row kernel ``ns_score_rows``
+  (``include/nsg_score.h``), which streams each position's logits once for the label's NLL and the row entropy, or
+  (``fused_head``) ``ns_lm_head_score``, the head GEMM with those scores as its epilogue.  ``ppl = exp(mean NLL)``
   over positions ``t < T-1`` with labels ``ids[t+1]`` (the Hugging Face shifted loss) and ``avg_entropy`` =
   mean row entropy over the same positions.
 """
@@ -86,10 +87,26 @@ def _fallback_entropy(text: str) -> float:
 
 
 class HipLMScorer:
-    """GPU perplexity / average-entropy scorer over a batched GPT-2 (``forward_sequences``) and the HIP
-    ``ns_score_rows`` kernel.  ``rows_per_batch`` bounds the padded ``B*T`` logits held at once."""
+    """GPU perplexity / average-entropy scorer over a batched GPT-2 and the HIP score kernels.
 
-    def __init__(self, batched_lm, tokenizer, *, rows_per_batch: int = 32768):
+    ``packed`` (default: on for a native model, which it needs): the texts of a group are packed back to back
+    (``BatchedGPT2.score_packed``: ragged attention, no padding row computed) and a group takes texts up to
+    ``rows_per_batch`` REAL rows.  A text's metrics have the same bits as on the padded path: the embedding, the
+    row-wise GEMMs and the attention are per sequence and batch-invariant.  ``packed=False`` keeps the padded
+    ``forward_sequences`` + ``ns_score_rows`` path (non-native models; the comparison leg), where ``rows_per_batch``
+    bounds the padded ``B*T`` logits rows held at once.
+
+    ``fused_head`` (default: off; needs ``packed``): the head GEMM and the row scores are one kernel,
+    ``ns_lm_head_score`` -- no logits array exists.  It sums the softmax in another order than ``ns_score_rows``, so
+    the last bits of the metrics differ from the default path's (both lie within 2e-5 relative of the float64 value),
+    which is why it is opt-in; a text still scores the same alone or in any batch.  With it on ``rows_per_batch``
+    bounds only the activation rows of a group (about ``20 * C`` bytes each: the residual, ln, attention, c_attn and
+    c_fc rows in fp16) plus 16 bytes per row and 512 columns of partial sums; nothing of size ``rows x V`` is
+    allocated.  A model whose width the kernel does not take (more than one accumulator chain, C > 1024) falls back
+    to the two launches."""
+
+    def __init__(self, batched_lm, tokenizer, *, rows_per_batch: int = 32768, packed: Optional[bool] = None,
+                 fused_head: bool = False):
         import torch
 
         if not torch.cuda.is_available():
@@ -98,6 +115,14 @@ class HipLMScorer:
             raise NativeLibraryError("HipLMScorer needs a ROCm GPU (ns_score_rows has no CPU path)")
         self.lm, self.tokenizer = batched_lm, tokenizer
         self.rows_per_batch = int(rows_per_batch)
+        native = bool(getattr(batched_lm, "native", False))
+        self.packed = native if packed is None else bool(packed)
+        self.fused_head = bool(fused_head)
+        if self.packed and not native:
+            raise ValueError("packed scoring needs the native HIP model (fp16 on the GPU)")
+        if self.fused_head and not self.packed:
+            raise ValueError("fused_head needs packed scoring")
+        self.last_rows = None  # {"rows": rows run by the last metrics_batch, "real": its texts' own rows, "groups"}
 
     @classmethod
     def from_provider(cls, provider, **kw) -> "HipLMScorer":
@@ -112,6 +137,27 @@ class HipLMScorer:
             ids = tok.encode(text)
         return [int(i) for i in ids]
 
+    def _row_scores_packed(self, seqs: List[List[int]]):
+        """:meth:`_row_scores` over packed texts: groups of whole texts, in order of length, of at most
+        ``rows_per_batch`` real rows (a longer single text runs alone)."""
+        from .lm.gpt2 import prefill_groups
+
+        out = [None] * len(seqs)
+        order = sorted(range(len(seqs)), key=lambda i: len(seqs[i]))
+        groups = prefill_groups([len(seqs[i]) for i in order], self.rows_per_batch)
+        for a, b in groups:
+            group = order[a:b]
+            nll, ent, start = self.lm.score_packed([seqs[g] for g in group], fused=self.fused_head)
+            nh, eh = nll.cpu().numpy(), ent.cpu().numpy()
+            for r, g in enumerate(group):
+                # per text, its own len - 1 rows summed on the host, as on the padded path
+                n = max(len(seqs[g]) - 1, 0)
+                lo = int(start[r])
+                out[g] = (float(nh[lo: lo + n].sum()), float(eh[lo: lo + n].sum()), len(seqs[g]))
+        rows = sum(len(q) for q in seqs)
+        self.last_rows = {"rows": rows, "real": rows, "groups": len(groups)}
+        return out
+
     def _row_scores(self, seqs: List[List[int]]):
         """Per sequence: (sum NLL over t < T-1, sum entropy over t < T-1, T)."""
         import numpy as np
@@ -120,6 +166,9 @@ class HipLMScorer:
         from . import _lib
         from .coder import _stream_handle
 
+        if self.packed:
+            return self._row_scores_packed(seqs)
+        run = ngroups = 0
         L = _lib.lib()
         V = self.lm.shape.vocab
         dt = _lib.NS_DTYPE_F16 if self.lm.logits_dtype == torch.float16 else _lib.NS_DTYPE_F32
@@ -133,6 +182,7 @@ class HipLMScorer:
                 j += 1
             group = order[i:j]
             T = max(len(seqs[g]) for g in group)
+            run, ngroups = run + len(group) * T, ngroups + 1
             ids = np.zeros((len(group), T), dtype=np.int64)
             labels = np.full((len(group), T), -1, dtype=np.int32)
             for r, g in enumerate(group):
@@ -158,6 +208,7 @@ class HipLMScorer:
                 out[g] = (float(nh[r, :n].sum()), float(eh[r, :n].sum()), len(seqs[g]))
             del logits, rows
             i = j
+        self.last_rows = {"rows": run, "real": sum(len(q) for q in seqs), "groups": ngroups}
         return out
 
     def metrics_batch(self, texts: Sequence[str]) -> List[Dict[str, float]]:
