@@ -111,6 +111,27 @@ int ns_decode_attention_paged(const void* d_qkv, int64_t qkv_stride, const uint6
                               int64_t done_stride, const int32_t* d_stop, void* d_out, int64_t out_stride, float scale,
                               void* hip_stream);
 
+/* ns_decode_attention_paged for the next C tokens of every stream in ONE launch (1 <= C <= 16): the decoder of a
+ * cover knows every token before its first step, so a stream's K/V pages are read once per C tokens instead of once
+ * per token.  d_qkv fp16 [B*C, qkv_stride] and d_out fp16 [B*C, out_stride]: stream b's query i is row b*C + i.
+ * d_count (int32 [B], device) = the new rows n_b of stream b, clamped to C; n_b <= 0 leaves the stream untouched.
+ * With L = d_lens[b], the call stores the k/v of rows i < n_b at positions L + i of b's pages (the one-token append's
+ * values: fp16 bit copies, fp8 the same conversion) and writes, for each i < n_b, the output row of query i over
+ * positions 0 .. L + i.  Output rows i >= n_b are never written; d_lens is not advanced (the caller adds d_count).
+ * Output row (b, i) and every stored page byte equal, bit for bit, what ns_decode_attention_paged produces when
+ * called i + 1 times in a row on the successive qkv rows with d_lens[b] = L, L + 1, ...: every query keeps the row
+ * split of its own key count (it may change inside a chunk), the chunk order, the per-row-group online softmax and
+ * the merge order of the one-token kernel.  There is no d_done / d_stop: d_count says who runs.
+ * Only table entries 0 .. max_chunks-1 are read.  A stream one of whose pages for rows L .. L + n_b - 1 is zero,
+ * misaligned or at a chunk >= max_chunks gets NaN in its n_b output rows and writes no page byte; a zero or
+ * misaligned entry of an already cached row is not read either and gives NaN rows.
+ * Returns NS_ERR_CONFIG for C outside [1, 16] or D != 64, NS_ERR_UNSUPPORTED for window > 0. */
+int ns_decode_attention_paged_chunk(const void* d_qkv, int64_t qkv_stride, const uint64_t* d_page_table,
+                                    int64_t table_stride, int max_chunks, int64_t layer_offset, const void* d_k_prefix,
+                                    const void* d_v_prefix, int64_t prefix_h_stride, int T0, int B, int H, int D,
+                                    const int32_t* d_lens, int window, int kv_format, int C, const int32_t* d_count,
+                                    void* d_out, int64_t out_stride, float scale, void* hip_stream);
+
 /* Causal attention over B whole sequences of T tokens (positions 0..T-1, no cache): the prefill of the shared
  * context (code_base/arithmetic.py:115-122, the first call), the guard's scoring forward
  * (src/neuralstego/metrics/lm_scorer.py:121-131) and the src provider's max_context window forward

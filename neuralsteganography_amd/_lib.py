@@ -37,7 +37,7 @@ EXPORTS = ("ns_create", "ns_destroy", "ns_last_error", "ns_version", "ns_max_top
            "ns_lm_layernorm_count",
            "ns_lm_embed_ln", "ns_lm_embed_seq_ln", "ns_seq_attention", "ns_lm_ln_gemm",
            "ns_decode_attention_paged", "ns_lm_embed_ln_rows", "ns_lm_layernorm_rows", "ns_seq_attention_ragged",
-           "ns_kv_copy_rows", "ns_seq_attention_ragged_past",
+           "ns_kv_copy_rows", "ns_seq_attention_ragged_past", "ns_decode_attention_paged_chunk",
            "ns_frac_create", "ns_frac_destroy", "ns_frac_last_error", "ns_frac_init", "ns_frac_encode_step",
            "ns_frac_decode_step", "ns_frac_set_slots", "ns_frac_scratch_bytes")
 NS_LM_EPI_STORE, NS_LM_EPI_GELU, NS_LM_EPI_RESIDUAL, NS_LM_EPI_STORE_F32 = 0, 1, 2, 3
@@ -169,6 +169,9 @@ def lib() -> ctypes.CDLL:
     L.ns_decode_attention_paged.restype = ci
     L.ns_decode_attention_paged.argtypes = [vp, i64, vp, i64, ci, i64, vp, vp, i64, ci, ci, ci, ci, vp, ci, ci, vp, i64,
                                             vp, vp, i64, ctypes.c_float, vp]
+    L.ns_decode_attention_paged_chunk.restype = ci
+    L.ns_decode_attention_paged_chunk.argtypes = [vp, i64, vp, i64, ci, i64, vp, vp, i64, ci, ci, ci, ci, vp, ci, ci, ci,
+                                                  vp, vp, i64, ctypes.c_float, vp]
     L.ns_lm_embed_ln_rows.restype = ci
     L.ns_lm_embed_ln_rows.argtypes = [vp, vp, vp, ci, ci, vp, vp, i64, vp, vp, vp, i64, ci, ci, ctypes.c_float, vp]
     L.ns_lm_layernorm_rows.restype = ci

@@ -1063,6 +1063,235 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(paged_waves
     }
 }
 
+// ------------------------------------------------------------------------------------ paged KV, C queries a stream
+// ns_decode_attention_paged_chunk (include/nsg_attn.h): stream b's next n <= C tokens in one launch, each query's
+// output the bits of the one-token kernel at that query's own key count.  Workgroup = one (stream, head) pair.
+//
+// The one-token kernel cuts query i (key count Lk = L + i + 1) into S = att_split(Lk) tasks, task w streaming the
+// 32-row chunks w, w + S, ... in order.  Queries of one launch with the same S have the same chunk sequences, so a
+// GROUP (S, w, query range) loads each chunk once and applies it to every query of the range whose key count reaches
+// it, one (m, l, acc) state per query in registers, CT queries at a time.  A chunk of at most 16 queries crosses at
+// most one of att_split's thresholds, so there are S groups, or S_lo + S_hi (at most 12) when it crosses one; the
+// waves take the groups round-robin.  Per query the operations are paged_chunk_math's, in the one-token kernel's row
+// order, with that kernel's choice between the interior and the general form; then paged_merge_groups, and either
+// paged_store_out (S = 1) or partials through LDS merged in split order with the one-token kernel's arithmetic.
+//
+// The n new rows are converted once (F::from_qkv), stored to the pages and kept in LDS; a chunk takes rows >= L from
+// there (the bytes an earlier one-token call would have stored and a later one loaded).  A row past a query's own
+// position is fed as the bit pattern 0 and masked, as the one-token kernel's short path feeds it (see there why the
+// bits cannot differ from the clamped copy the general path feeds).  Pages are only read below L and only written at
+// L .. L + n - 1, so no wave reads what another writes.
+constexpr int ATT_CHUNK_MAX = 16;
+
+template <class F, int CT, int NW>
+__global__ __launch_bounds__(64 * NW) void paged_attn_chunk_kernel(const PagedArgs a, const int C,
+                                                                   const int32_t* __restrict__ count) {
+    typedef typename F::Elem E;
+    typedef typename F::Raw Raw;
+    constexpr int DPL = F::DPL, LPR = F::LPR, RPI = F::RPI, NI = F::NI;
+    static_assert(RPI * NI == 32, "one iteration = one page's worth of rows");
+    __shared__ float s_m[ATT_CHUNK_MAX][8], s_l[ATT_CHUNK_MAX][8];
+    __shared__ float s_acc[ATT_CHUNK_MAX][8][ATT_D];
+    __shared__ Raw s_kn[ATT_CHUNK_MAX][LPR], s_vn[ATT_CHUNK_MAX][LPR];  // the new rows, as the pages hold them
+    __shared__ __attribute__((aligned(16))) _Float16 s_q[ATT_CHUNK_MAX][ATT_D];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int b = blockIdx.x / a.H, h = blockIdx.x - b * a.H;
+    const int n = min(count[b], C);
+    if (n <= 0) return;  // uniform over the workgroup: the stream is left untouched
+    const int L = a.lens[b];
+    const int T0 = a.T0;
+    const int HD = a.H * ATT_D;
+    const uint64_t* trow = a.table + (int64_t)b * a.tstride;
+    // the pages of the new rows (stream rows jn .. jn + n - 1: at most two chunks) must exist
+    const int64_t jn = (int64_t)L - T0;
+    bool bad = jn < 0 || ((jn + n - 1) >> 5) >= a.max_chunks;
+    uint64_t pn0 = 0, pn1 = 0;
+    if (!bad) {
+        pn0 = trow[jn >> 5];
+        pn1 = trow[(jn + n - 1) >> 5];
+        bad = pn0 == 0 || (pn0 & 15u) || pn1 == 0 || (pn1 & 15u);
+    }
+    if (bad) {  // uniform: NaN rows (the coder rejects them), no page byte written
+        if (tid < ATT_D)
+            for (int i = 0; i < n; ++i)
+                a.out[((int64_t)b * C + i) * a.out_stride + h * ATT_D + tid] = (_Float16)__builtin_nanf("");
+        return;
+    }
+    const int64_t hbase = a.layer_off + (int64_t)h * 32 * ATT_D;  // this layer's K rows of head h in a page
+    if (tid < n * LPR) {  // convert, append and keep the new rows; q rows to LDS
+        const int i = tid / LPR, cc = tid % LPR;
+        const _Float16* qrow = a.qkv + ((int64_t)b * C + i) * a.qkv_stride + h * ATT_D + cc * DPL;
+        const Raw kn = F::from_qkv(qrow + HD), vn = F::from_qkv(qrow + 2 * HD);
+        s_kn[i][cc] = kn;
+        s_vn[i][cc] = vn;
+#pragma unroll
+        for (int h8 = 0; h8 < DPL / 8; ++h8) *(f16x8*)&s_q[i][cc * DPL + h8 * 8] = *(const f16x8*)(qrow + h8 * 8);
+        const int64_t jj = jn + i;
+        E* kd = (E*)((jj >> 5) == (jn >> 5) ? pn0 : pn1) + hbase + (jj & 31) * ATT_D + cc * DPL;
+        *(Raw*)kd = kn;
+        *(Raw*)(kd + a.v_off) = vn;
+    }
+    __syncthreads();
+    const int g = lane / LPR;  // row within an RPI-row slab
+    const int c = lane % LPR;  // DPL-dim slice
+    // groups: queries [0, ib) split S_lo ways, queries [ib, n) S_hi ways (ib = n when no threshold is crossed)
+    const int S_lo = att_split(L + 1), S_hi = att_split(L + n);
+    const int ib = S_lo == S_hi ? n : S_lo * NSG_ATT_ROWS1 - L;  // first query whose key count exceeds the threshold
+    const int ngroups = S_lo == S_hi ? S_lo : S_lo + S_hi;
+    const int cl = L > T0 ? (L - 1 - T0) >> 5 : -1;  // the last chunk holding a cached stream row (< max_chunks)
+    const E* kpb = (const E*)a.kp + (int64_t)h * a.ph + c * DPL;
+    const E* vpb = (const E*)a.vp + (int64_t)h * a.ph + c * DPL;
+    const int64_t hoff = hbase + c * DPL;
+    for (int gi = wave; gi < ngroups; gi += NW) {  // wave-uniform
+        const bool lo = gi < S_lo;
+        const int S = lo ? S_lo : S_hi, w = lo ? gi : gi - S_lo;
+        const int i_beg = lo ? 0 : ib, i_end = lo ? ib : n;
+        for (int q0 = i_beg; q0 < i_end; q0 += CT) {
+            const int nq = min(CT, i_end - q0);
+            float m[CT], l[CT], acc[CT][DPL];
+#pragma unroll
+            for (int ii = 0; ii < CT; ++ii) {
+                m[ii] = -1e30f;
+                l[ii] = 0.0f;
+#pragma unroll
+                for (int d = 0; d < DPL; ++d) acc[ii][d] = 0.0f;
+            }
+            bool hole = false;  // a cached row's table entry is zero or misaligned: nothing read there, NaN rows
+            int pbase = -1;     // lane i holds table entry pbase + i (entries of cached rows only)
+            uint64_t pgv = 0;
+            const int Lmax = L + q0 + nq;  // the key count of the batch's last query
+            for (int j0 = w * RPI * NI; j0 < Lmax; j0 += S * RPI * NI) {
+                Raw kr[NI], vr[NI];
+                const int ca = max(j0 - T0, 0) >> 5;  // the chunk of the first stream row of the iteration
+                uint64_t pa = 0, pb = 0;
+                if (ca <= cl) {
+                    if (pbase < 0 || ca + 1 >= pbase + 64) {
+                        pbase = ca;
+                        pgv = ca + lane <= cl ? trow[ca + lane] : 0;
+                    }
+                    pa = readlane64(pgv, ca - pbase);
+                    pb = readlane64(pgv, ca + 1 - pbase);
+                    if (pa & 15u) pa = 0;
+                    if (pb & 15u) pb = 0;
+                }
+                if (j0 >= T0 && j0 + RPI * NI <= L && pa != 0 && (pb != 0 || ((j0 - T0) & 31) == 0)) {
+                    const int jj0 = j0 - T0;  // cached stream rows only, in at most two pages
+#pragma unroll
+                    for (int u = 0; u < NI; ++u) {
+                        const int jj = jj0 + RPI * u + g;
+                        const E* ka = (const E*)((jj >> 5) == ca ? pa : pb) + hoff + (int64_t)(jj & 31) * ATT_D;
+                        kr[u] = att_load((const Raw*)ka);
+                        vr[u] = att_load((const Raw*)(ka + a.v_off));
+                    }
+                } else {
+#pragma unroll
+                    for (int u = 0; u < NI; ++u) {
+                        const int row = j0 + RPI * u + g;
+                        kr[u] = Raw{};
+                        vr[u] = Raw{};
+                        if (row < T0) {
+                            kr[u] = *(const Raw*)(kpb + (int64_t)row * ATT_D);
+                            vr[u] = *(const Raw*)(vpb + (int64_t)row * ATT_D);
+                        } else if (row < L) {
+                            const int jj = row - T0;
+                            const uint64_t pg = (jj >> 5) == ca ? pa : pb;
+                            if (pg != 0) {
+                                const E* ka = (const E*)pg + hoff + (int64_t)(jj & 31) * ATT_D;
+                                kr[u] = att_load((const Raw*)ka);
+                                vr[u] = att_load((const Raw*)(ka + a.v_off));
+                            } else {
+                                hole = true;
+                            }
+                        } else if (row < L + n) {
+                            kr[u] = s_kn[row - L][c];
+                            vr[u] = s_vn[row - L][c];
+                        }
+                    }
+                }
+#pragma unroll
+                for (int ii = 0; ii < CT; ++ii) {
+                    const int L0 = L + q0 + ii;  // query q0 + ii attends to positions 0 .. L0
+                    if (ii >= nq || j0 > L0) continue;  // uniform
+                    const typename F::Q q = F::load_q(&s_q[q0 + ii][c * DPL]);
+                    if (j0 >= T0 && j0 + RPI * NI <= L0) {  // the one-token kernel's interior iteration
+                        paged_chunk_math<F, false>(q, kr, vr, j0 + g, L0, kr[0], vr[0], a.scale_log2, m[ii], l[ii],
+                                                   acc[ii]);
+                    } else {
+                        Raw kq[NI], vq[NI];
+#pragma unroll
+                        for (int u = 0; u < NI; ++u) {
+                            const bool own = j0 + RPI * u + g <= L0;
+                            kq[u] = own ? kr[u] : Raw{};
+                            vq[u] = own ? vr[u] : Raw{};
+                        }
+                        const Raw knew = s_kn[q0 + ii][c], vnew = s_vn[q0 + ii][c];
+                        paged_chunk_math<F, true>(q, kq, vq, j0 + g, L0, knew, vnew, a.scale_log2, m[ii], l[ii],
+                                                  acc[ii]);
+                    }
+                }
+            }
+            hole = __any(hole);
+#pragma unroll
+            for (int ii = 0; ii < CT; ++ii) {
+                if (ii >= nq) continue;  // uniform
+                const int i = q0 + ii;
+                paged_merge_groups<F>(m[ii], l[ii], acc[ii]);
+                if (hole) {
+                    m[ii] = l[ii] = __builtin_nanf("");
+#pragma unroll
+                    for (int d = 0; d < DPL; ++d) acc[ii][d] = __builtin_nanf("");
+                }
+                if (S == 1) {  // the whole query in this wave
+                    if (g == 0)
+                        paged_store_out<F>(a.out + ((int64_t)b * C + i) * a.out_stride + h * ATT_D + c * DPL, l[ii],
+                                           acc[ii]);
+                } else if (g == 0) {
+#pragma unroll
+                    for (int d = 0; d < DPL; ++d) s_acc[i][w][c * DPL + d] = acc[ii][d];
+                    if (c == 0) {
+                        s_m[i][w] = m[ii];
+                        s_l[i][w] = l[ii];
+                    }
+                }
+            }
+        }
+    }
+    if (S_hi <= 1) return;  // uniform: no query was split over waves
+    __syncthreads();
+    // queries split over S > 1 tasks: merge the S partials in split order, as the one-token kernel does
+    if (lane >= LPR) return;
+    for (int i = wave; i < n; i += NW) {
+        const int S = att_split(L + i + 1);
+        if (S <= 1) continue;
+        float mt = s_m[i][0];
+        for (int w = 1; w < S; ++w) mt = fmaxf(mt, s_m[i][w]);
+        float l = 0.0f;
+        float acc[DPL];
+#pragma unroll
+        for (int d = 0; d < DPL; ++d) acc[d] = 0.0f;
+        for (int w = 0; w < S; ++w) {
+            const float f = exp2f(s_m[i][w] - mt);
+            l += s_l[i][w] * f;
+#pragma unroll
+            for (int d = 0; d < DPL; ++d) acc[d] += s_acc[i][w][lane * DPL + d] * f;
+        }
+        const float inv = 1.0f / l;
+#pragma unroll
+        for (int h8 = 0; h8 < DPL / 8; ++h8) {
+            f16x8 o;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                float tv = acc[h8 * 8 + k] * inv;
+                asm volatile("" : "+v"(tv));
+                o[k] = (_Float16)tv;
+            }
+            *(f16x8*)(a.out + ((int64_t)b * C + i) * a.out_stride + h * ATT_D + lane * DPL + h8 * 8) = o;
+        }
+    }
+}
+
 // fp16 -> fp8 (e4m3fn) with the same saturating round-to-nearest-even conversion as the kernel's KV append
 __global__ void quantize_fp8_kernel(const _Float16* __restrict__ src, uint32_t* __restrict__ dst, int64_t n4) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1503,6 +1732,76 @@ extern "C" int ns_decode_attention_paged(const void* d_qkv, int64_t qkv_stride, 
     a.scale_log2 = scale * 1.4426950408889634f;
     return kv_format == NS_KV_FP8 ? paged_attention<nsg::FmtF8>(a, hip_stream)
                                   : paged_attention<nsg::FmtF16>(a, hip_stream);
+}
+
+template <class F, int CTMAX>
+static int paged_attention_chunk(const nsg::PagedArgs& a, int C, const int32_t* d_count, void* hip_stream) {
+    const hipStream_t st = (hipStream_t)hip_stream;
+    const dim3 grid(a.B * a.H);
+    // CT = queries a wave keeps in registers at once (the smallest power of two >= C, at most CTMAX: more queries
+    // stream their chunks again); placement only, a query's arithmetic does not depend on it
+    if (C <= 1)
+        hipLaunchKernelGGL((nsg::paged_attn_chunk_kernel<F, 1, 8>), grid, dim3(512), 0, st, a, C, d_count);
+    else if (C <= 2)
+        hipLaunchKernelGGL((nsg::paged_attn_chunk_kernel<F, 2, 8>), grid, dim3(512), 0, st, a, C, d_count);
+    else if (C <= 4)
+        hipLaunchKernelGGL((nsg::paged_attn_chunk_kernel<F, 4, 8>), grid, dim3(512), 0, st, a, C, d_count);
+    else if (C <= 8 || CTMAX <= 8)
+        hipLaunchKernelGGL((nsg::paged_attn_chunk_kernel<F, 8, 8>), grid, dim3(512), 0, st, a, C, d_count);
+    else
+        hipLaunchKernelGGL((nsg::paged_attn_chunk_kernel<F, CTMAX, 4>), grid, dim3(256), 0, st, a, C, d_count);
+    return hipGetLastError() == hipSuccess ? NS_OK : NS_ERR_HIP;
+}
+
+extern "C" int ns_decode_attention_paged_chunk(const void* d_qkv, int64_t qkv_stride, const uint64_t* d_page_table,
+                                               int64_t table_stride, int max_chunks, int64_t layer_offset,
+                                               const void* d_k_prefix, const void* d_v_prefix,
+                                               int64_t prefix_h_stride, int T0, int B, int H, int D,
+                                               const int32_t* d_lens, int window, int kv_format, int C,
+                                               const int32_t* d_count, void* d_out, int64_t out_stride, float scale,
+                                               void* hip_stream) {
+    if (!d_qkv || !d_page_table || !d_lens || !d_count || !d_out || B <= 0 || H <= 0 || T0 < 0 || layer_offset < 0 ||
+        window < 0)
+        return NS_ERR_CONFIG;
+    if (C < 1 || C > nsg::ATT_CHUNK_MAX || D != nsg::ATT_D) return NS_ERR_CONFIG;
+    if (window > 0) return NS_ERR_UNSUPPORTED;
+    if (kv_format != NS_KV_FP16 && kv_format != NS_KV_FP8) return NS_ERR_CONFIG;
+    if (max_chunks < 1 || table_stride < max_chunks) return NS_ERR_CONFIG;
+    const int64_t esz = kv_format == NS_KV_FP8 ? 1 : 2;
+    if (T0 > 0 && (!d_k_prefix || !d_v_prefix || prefix_h_stride < (int64_t)T0 * D || ((prefix_h_stride * esz) & 15)))
+        return NS_ERR_CONFIG;
+    const uintptr_t align = (uintptr_t)d_qkv | (uintptr_t)d_out | (uintptr_t)(T0 > 0 ? d_k_prefix : d_qkv) |
+                            (uintptr_t)(T0 > 0 ? d_v_prefix : d_qkv);
+    if ((align & 15u) || (qkv_stride & 7) || (out_stride & 7) || (((uintptr_t)d_lens | (uintptr_t)d_count) & 3u) ||
+        ((uintptr_t)d_page_table & 7u))
+        return NS_ERR_CONFIG;
+    if (qkv_stride < 3LL * H * D || out_stride < (int64_t)H * D) return NS_ERR_CONFIG;
+    if ((int64_t)B * H > 0x7FFFFFFF) return NS_ERR_UNSUPPORTED;
+    if (layer_offset % (16 / esz)) return NS_ERR_CONFIG;  // 16-byte rows
+    nsg::PagedArgs a;
+    a.qkv = (const _Float16*)d_qkv;
+    a.qkv_stride = qkv_stride;
+    a.table = d_page_table;
+    a.tstride = table_stride;
+    a.max_chunks = max_chunks;
+    a.v_off = (int64_t)H * 32 * D;
+    a.layer_off = layer_offset;
+    a.kp = T0 > 0 ? d_k_prefix : d_qkv;
+    a.vp = T0 > 0 ? d_v_prefix : d_qkv;
+    a.ph = prefix_h_stride;
+    a.T0 = T0;
+    a.B = B;
+    a.H = H;
+    a.lens = d_lens;
+    a.window = 0;
+    a.done = nullptr;
+    a.done_stride = 0;
+    a.stop = nullptr;
+    a.out = (_Float16*)d_out;
+    a.out_stride = out_stride;
+    a.scale_log2 = scale * 1.4426950408889634f;
+    return kv_format == NS_KV_FP8 ? paged_attention_chunk<nsg::FmtF8, 8>(a, C, d_count, hip_stream)
+                                  : paged_attention_chunk<nsg::FmtF16, 16>(a, C, d_count, hip_stream);
 }
 
 extern "C" int ns_quantize_fp8(const void* d_src, void* d_dst, int64_t n, void* hip_stream) {

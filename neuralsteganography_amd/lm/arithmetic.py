@@ -430,16 +430,25 @@ class HipArithmeticLM:
                      contexts: Optional[Sequence[Sequence[int]]] = None,
                      quality: Optional[Mapping[str, object]] = None,
                      qualities: Optional[Sequence[Mapping[str, object]]] = None, graphs: Optional[bool] = None,
-                     slots: Optional[int] = None) -> List[List[int]]:
+                     slots: Optional[int] = None, chunk: int = 1) -> List[List[int]]:
         """Decode token lists (ragged); returns every emitted bit (callers truncate).  On the native GPU model the
         lists run through ``slots`` slots (:class:`~neuralsteganography_amd.lm.slots.SlotDecoder`, longest first,
         a message's pages mapped when it is admitted); with ``graphs`` the per-token step (coder + GPT-2 decode) is a
         replayed hipGraph, as in :meth:`encode_batch`.  Non-native models ignore ``graphs`` (eager lockstep loop).
         ``context`` / ``contexts`` as in :meth:`encode_batch`: one shared context, or one per token list; ``quality``
         / ``qualities`` likewise (one mixed batch, top-k beyond the single-pass limit grouped,
-        ``last_decode_schedule["quality_groups"]``)."""
+        ``last_decode_schedule["quality_groups"]``).
+        ``chunk`` = C in 2..16 (native model, no attention window; default 1 = one token per step): every cover token
+        is known before the first step, so a slot's next C tokens go through the LM in ONE forward
+        (``SlotDecoder.run_chunk``; its K/V pages are read once per C tokens) and only the coder runs token by token --
+        the same bits.  The slot count is then ``min(B, max(1, slots // C))``: a forward has at most ``slots`` rows,
+        so activations and logits take no more memory than ``slots`` was sized for."""
         from ..codec.errors import DecodeDivergenceError
+        from .slots import check_chunk
 
+        chunk = check_chunk(chunk)
+        if chunk > 1 and (not getattr(self.lm, "native", False) or getattr(self.lm, "window", 0) > 0):
+            raise ValueError("chunk > 1 needs the native HIP step without an attention window")
         B = len(token_lists)
         context, contexts = _one_or_many(context, contexts, B)
         quality, plist = self._quality_or_many(quality, qualities, B)
@@ -448,7 +457,7 @@ class HipArithmeticLM:
         groups = _quality_groups(plist, self._single_pass_limit()) if plist is not None else None
         if groups is not None and len(groups) > 1:
             res = self._by_group(self.decode_batch, token_lists, groups, context, contexts, qualities, False,
-                                 graphs=graphs, slots=slots)
+                                 graphs=graphs, slots=slots, chunk=chunk)
             self.last_decode_schedule = dict(getattr(self, "last_decode_schedule", None) or {},
                                              quality_groups=len(groups))
             return res
@@ -467,11 +476,14 @@ class HipArithmeticLM:
             from .slots import SlotDecoder
 
             S = max(1, min(B, int(slots) if slots else self.max_batch))
-            dec = SlotDecoder(self, self._coder(params, S, mixed=sq is not None), token_lists, context, slots=S,
+            # chunk > 1: the slot rule min(B, max(1, slots // chunk)) applies to the caller's slots, not to min(B, slots)
+            dec = SlotDecoder(self, self._coder(params, S, mixed=sq is not None), token_lists, context,
+                              slots=S if chunk == 1 else (int(slots) if slots else self.max_batch),
                               use_graph=bool(graphs), compact=self.slot_compaction, contexts=contexts,
-                              share=self.share_contexts, qualities=sq, share_prefixes=self.share_prefixes)
+                              share=self.share_contexts, qualities=sq, share_prefixes=self.share_prefixes,
+                              chunk=chunk, check_every=max(1, 16 // chunk))  # a host check about every 16 tokens
             out = dec.run()
-            self.last_decode_schedule = {"slots": S, "evictions": dec.evictions, "compactions": dec.compactions,
+            self.last_decode_schedule = {"slots": dec.S, "chunk": chunk, "evictions": dec.evictions, "compactions": dec.compactions,
                                          "prefill_rows": dec.prefill_rows, "prefill_groups": dec.prefill_groups,
                                          "prefill_shared": dec.prefill_shared, "quality_groups": 1}
             if dec.prefix_entries:

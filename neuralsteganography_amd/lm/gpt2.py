@@ -1030,6 +1030,148 @@ class BatchedGPT2:
         self.L += 1
         return self._logits(h[:, -1])
 
+    # ------------------------------------------------------------------ several KNOWN tokens per forward (decoder)
+    def _chunk_check(self, C: int) -> int:
+        from .slots import check_chunk
+
+        C = check_chunk(C)
+        if not self.native:
+            raise ValueError("chunked decode steps need the native HIP step (fp16 on the GPU)")
+        if self.window > 0:
+            raise ValueError("chunked decode steps do not support a sliding attention window")
+        return C
+
+    def _chunk_buffers(self, B: int, C: int):
+        """Activation buffers of the chunked step (M = B * C rows) and its per-row cache lengths, fixed addresses."""
+        cb = getattr(self, "_cb", None)
+        if cb is None or cb["key"] != (B, C):
+            n, dev, dt, M = self.shape.n_embd, self.device, self.dtype, B * C
+            cb = self._cb = {"key": (B, C), "h": torch.empty((M, n), device=dev, dtype=dt),
+                             "a": torch.empty((M, n), device=dev, dtype=dt),
+                             "qkv": torch.empty((M, 3 * n), device=dev, dtype=dt),
+                             "o": torch.zeros((M, n), device=dev, dtype=dt),
+                             "f": torch.empty((M, 4 * n), device=dev, dtype=dt),
+                             "ar": torch.arange(C, device=dev, dtype=torch.int32).unsqueeze(0),
+                             "rowlens": torch.empty((B, C), device=dev, dtype=torch.int32),
+                             "cnt": torch.empty((B,), device=dev, dtype=torch.int32)}
+        return cb
+
+    def _decode_chunk_native(self, tokens: torch.Tensor, counts: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+        """:meth:`_decode_native` over the next ``C`` tokens of every stream at once (M = B * C rows, stream b's token
+        i at row b * C + i and position ``lens[b] + i``): the same launches, with ``ns_decode_attention_paged_chunk``
+        -- every query the one-token kernel's arithmetic at its own key count -- as the attention, a plain ln_f and
+        ``lens += counts`` as one device op.  Row (b, i) of ``out`` ([B, C, ld]) holds, for i < counts[b], the bits
+        :meth:`step` returns for stream b after its tokens 0 .. i were fed one at a time; rows i >= counts[b] are not
+        meaningful.  No host synchronisation, no allocation."""
+        from .. import _lib
+        from ..coder import _stream_handle
+
+        kv = self.kv
+        B = kv.B
+        if tokens.dim() != 2 or tokens.shape[0] != B or tokens.dtype != torch.int32 or not tokens.is_contiguous():
+            raise ValueError(f"tokens must be a contiguous int32 [{B}, C] tensor")
+        C = self._chunk_check(tokens.shape[1])
+        if counts.shape != (B,) or counts.dtype != torch.int32 or not counts.is_contiguous() or \
+                not _same_device(counts.device, self.device):
+            raise ValueError(f"counts must be a contiguous int32 [{B}] tensor on {self.device}")
+        if out.shape != (B, C, self.ld) or not out.is_contiguous():
+            raise ValueError(f"logits buffer must be a contiguous [{B}, {C}, {self.ld}] tensor")
+        L = _lib.lib()
+        st = _stream_handle()
+        s = self.shape
+        n = s.n_embd
+        H, D = s.n_head, n // s.n_head
+        M = B * C
+        cb = self._chunk_buffers(B, C)
+        h, a, qkv, o, f = (cb[k].data_ptr() for k in ("h", "a", "qkv", "o", "f"))
+        ldq, ldf = cb["qkv"].stride(0), cb["f"].stride(0)
+        T0 = kv.T0
+        eps = float(s.eps)
+        torch.add(kv.lens.unsqueeze(1), cb["ar"], out=cb["rowlens"])  # row (b, i): position lens[b] + i
+        torch.clamp(counts, 0, C, out=cb["cnt"])
+
+        def gemm(x, ldx, wt, bias, y, ldy, epi, N, K):
+            _check(L.ns_lm_gemm(x, ldx, wt.data_ptr(), wt.stride(0), bias.data_ptr() if bias is not None else None,
+                                y, ldy, M, N, K, epi, st), "ns_lm_gemm")
+
+        def ln_gemm(ln_w, ln_b, wt, bias, y, ldy, epi, N):
+            _check(L.ns_lm_ln_gemm(h, n, ln_w.data_ptr(), ln_b.data_ptr(), eps, wt.data_ptr(), wt.stride(0),
+                                   bias.data_ptr(), y, ldy, M, N, n, epi, a, n, st), "ns_lm_ln_gemm")
+
+        lens, table, cnt = kv.lens.data_ptr(), kv.table.data_ptr(), cb["cnt"].data_ptr()
+        lw0 = self.layers[0]
+        _check(L.ns_lm_embed_ln_rows(tokens.data_ptr(), self.wte.data_ptr(), self.wpe.data_ptr(), s.vocab,
+                                     s.n_positions, cb["rowlens"].data_ptr(), h, n, lw0["ln1_w"].data_ptr(),
+                                     lw0["ln1_b"].data_ptr(), a, n, M, n, eps, st), "ns_lm_embed_ln_rows")
+        for i, lw in enumerate(self.layers):
+            if i > 0:
+                ln_gemm(lw["ln1_w"], lw["ln1_b"], lw["qkv_wt"], lw["qkv_b"], qkv, ldq, _lib.NS_LM_EPI_STORE, 3 * n)
+            else:
+                gemm(a, n, lw["qkv_wt"], lw["qkv_b"], qkv, ldq, _lib.NS_LM_EPI_STORE, 3 * n, n)
+            kp = self.kp[i, 0] if T0 else None
+            vp = self.vp[i, 0] if T0 else None
+            _check(L.ns_decode_attention_paged_chunk(qkv, ldq, table, kv.table.stride(0), kv.width,
+                                                     kv.pool.layer_offset(i), kp.data_ptr() if T0 else None,
+                                                     vp.data_ptr() if T0 else None, kp.stride(0) if T0 else 0, T0, B,
+                                                     H, D, lens, 0, self._kv_format, C, cnt, o, n,
+                                                     1.0 / math.sqrt(D), st), "ns_decode_attention_paged_chunk")
+            gemm(o, n, lw["o_wt"], lw["o_b"], h, n, _lib.NS_LM_EPI_RESIDUAL, n, n)
+            ln_gemm(lw["ln2_w"], lw["ln2_b"], lw["fc_wt"], lw["fc_b"], f, ldf, _lib.NS_LM_EPI_GELU, 4 * n)
+            gemm(f, ldf, lw["pr_wt"], lw["pr_b"], h, n, _lib.NS_LM_EPI_RESIDUAL, n, 4 * n)
+        _check(L.ns_lm_layernorm(h, n, self.lnf_w.data_ptr(), self.lnf_b.data_ptr(), a, n, M, n, eps, st),
+               "ns_lm_layernorm")
+        epi = _lib.NS_LM_EPI_STORE_F32 if out.dtype == torch.float32 else _lib.NS_LM_EPI_STORE
+        gemm(a, n, self.head_t, None, out.data_ptr(), out.stride(1), epi, self.ld, n)
+        kv.lens.add_(cb["cnt"])  # after every layer has read the lengths
+        return out
+
+    def begin_chunk_static(self, logits_out: torch.Tensor) -> None:
+        """Prepare :meth:`step_chunk_static`: the logits of ``C`` tokens per stream go to the fixed buffer
+        ``logits_out`` ([B, C, ld]), so one captured hipGraph replays every chunked step."""
+        if logits_out.dim() != 3:
+            raise ValueError("static chunk logits must be [B, C, ld]")
+        C = self._chunk_check(logits_out.shape[1])
+        if logits_out.shape != (self.kv.B, C, self.ld) or logits_out.dtype != self.logits_dtype:
+            raise ValueError(f"static chunk logits must be [{self.kv.B}, {C}, {self.ld}] {self.logits_dtype}")
+        self._static_chunk_logits = logits_out
+        self._chunk_buffers(self.kv.B, C)  # allocated here, outside any capture
+
+    @torch.no_grad()
+    def step_chunk_static(self, tokens: torch.Tensor, counts: torch.Tensor) -> torch.Tensor:
+        """Feed the next ``counts[b] <= C`` known tokens of every stream (``tokens`` int32 [B, C], ``counts`` int32
+        [B], both on the device) in ONE forward into the :meth:`begin_chunk_static` buffer.  No host-side page
+        mapping or length bookkeeping (the caller maps pages for ``lens + counts`` ahead and calls
+        :meth:`advance_rows`), no host synchronisation, no allocation: capturable as a graph."""
+        return self._decode_chunk_native(tokens, counts, self._static_chunk_logits)
+
+    @torch.no_grad()
+    def step_chunk(self, tokens: torch.Tensor, counts) -> torch.Tensor:
+        """:meth:`step_chunk_static` with the pages reserved and the host lengths advanced here, into a fresh
+        ``[B, C, ld]`` tensor (``counts``: host ints, one per stream, each in [0, C])."""
+        from ..exceptions import KVCapacityError
+
+        B = self.kv.B
+        if tokens.dim() != 2 or tokens.shape[0] != B:
+            raise ValueError(f"expected [{B}, C] tokens")
+        C = self._chunk_check(tokens.shape[1])
+        cnt = np.asarray(counts, dtype=np.int64).reshape(B)
+        if (cnt < 0).any() or (cnt > C).any():
+            raise ValueError(f"counts must lie in [0, {C}]")
+        run = np.nonzero(cnt > 0)[0]
+        if self.kv.ensure(run, self.kv.lens_host[run] + cnt[run]).size:
+            raise KVCapacityError(f"KV cache full for B={B}: no device memory for a page")
+        out = torch.empty((B, C, self.ld), device=self.device, dtype=self.logits_dtype)
+        self._decode_chunk_native(tokens.to(device=self.device, dtype=torch.int32).contiguous(),
+                                  torch.from_numpy(cnt.astype(np.int32)).to(self.device), out)
+        self.advance_rows(cnt)
+        return out
+
+    def advance_rows(self, counts) -> None:
+        """The host side of one executed chunked step: stream b moved ``counts[b]`` positions (:meth:`advance` with
+        one count per stream)."""
+        cnt = np.asarray(counts, dtype=np.int64).reshape(self.kv.B)
+        self.L += int(cnt.max(initial=0))
+        self.kv.advance_rows(cnt)
 
 def ragged_blocks(lengths):
     """Host side of ``ns_seq_attention_ragged`` for sequences of ``lengths`` rows packed back to back:

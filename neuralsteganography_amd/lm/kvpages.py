@@ -505,6 +505,10 @@ class PagedKV:
     def advance(self, n: int = 1) -> None:
         self.lens_host += int(n)
 
+    def advance_rows(self, counts) -> None:
+        """:meth:`advance` with one count per slot (a chunked decode step moves a slot by the tokens it fed)."""
+        self.lens_host += np.asarray(counts, dtype=np.int64).reshape(self.B)
+
     def steps_reserved(self, slots) -> int:
         """Decode steps every slot in ``slots`` can still take within its pages."""
         slots = np.asarray(slots, dtype=np.int64).reshape(-1)

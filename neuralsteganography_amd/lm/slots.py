@@ -46,6 +46,38 @@ from ..coder import EncodeSession, _state_fields, _stats_rows
 from ..exceptions import KVCapacityError
 
 
+MAX_CHUNK = 16  # tokens of a stream per forward: ns_decode_attention_paged_chunk's limit
+
+
+def check_chunk(chunk) -> int:
+    """``chunk`` (known tokens of a stream per LM forward) as an int in 1..16, else ``ValueError``."""
+    if isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)):
+        raise ValueError(f"chunk must be an int in 1..{MAX_CHUNK}, got {chunk!r}")
+    if not 1 <= int(chunk) <= MAX_CHUNK:
+        raise ValueError(f"chunk must be in 1..{MAX_CHUNK}, got {chunk}")
+    return int(chunk)
+
+
+def chunk_slots(n_messages: int, slots: int, chunk: int) -> int:
+    """Slots of a decode that feeds ``chunk`` tokens per stream and forward: ``min(N, max(1, slots // chunk))``, so a
+    forward has at most ``slots`` rows -- the activations and the logits take no more memory than the caller sized
+    ``slots`` for (``chunk = 1``: ``min(N, slots)``, at least one)."""
+    return max(1, min(int(n_messages), max(1, int(slots) // int(chunk))))
+
+
+def chunk_counts(fed, nlen, chunk: int) -> np.ndarray:
+    """Tokens each slot takes in the next chunked iteration: ``min(chunk, remaining)`` with ``remaining = nlen - fed``
+    (never negative: a finished or empty slot takes none)."""
+    return np.clip(np.asarray(nlen, dtype=np.int64) - np.asarray(fed, dtype=np.int64), 0, int(chunk))
+
+
+def chunk_page_horizon(lens, ends, check_every: int, chunk: int) -> np.ndarray:
+    """Positions below which a live slot needs pages until the next host check has mapped more: the next
+    ``(check_every + 1) * chunk`` positions, capped at the message's end (``ends`` = context + token count)."""
+    lens = np.asarray(lens, dtype=np.int64)
+    return np.minimum(lens + (int(check_every) + 1) * int(chunk), np.asarray(ends, dtype=np.int64))
+
+
 class _SlotGraph:
     """``body()`` (one whole step into fixed buffers) run once eagerly on a side stream -- a real step, which also
     warms every kernel up -- then captured as a hipGraph and replayed per later step."""
@@ -523,12 +555,20 @@ class SlotDecoder:
     def __init__(self, provider, ctx, token_lists: Sequence[Sequence[int]], context: Sequence[int], *, slots: int,
                  use_graph: bool, check_every: int = 16, compact: bool = True,
                  contexts: Optional[Sequence[Sequence[int]]] = None, share: bool = True, qualities=None,
-                 share_prefixes: bool = True):
+                 share_prefixes: bool = True, chunk: int = 1):
         self.p, self.lm, self.ctx = provider, provider.lm, ctx
         self.qual = qualities  # coder.StreamQuality with one row per message, or None
         self.lists = token_lists
         self.N = len(token_lists)
-        self.S = max(1, min(int(slots), self.N))
+        # chunk = C > 1: every iteration feeds a slot's next C known tokens in one forward (run_chunk), through
+        # min(N, max(1, slots // C)) slots -- a forward then has at most ``slots`` rows
+        self.C = check_chunk(chunk)
+        if self.C > 1:
+            if not getattr(self.lm, "native", False):
+                raise ValueError("chunk > 1 needs the native HIP step")
+            if getattr(self.lm, "window", 0) > 0:
+                raise ValueError("chunk > 1 does not support a sliding attention window")
+        self.S = chunk_slots(self.N, slots, self.C)
         self.context = context
         self.contexts = _trimmed(contexts, self.N) if contexts is not None else None  # one per message
         self.keys, self.shares = _multiplicity(self.contexts, share) if contexts is not None else (None, None)
@@ -540,11 +580,15 @@ class SlotDecoder:
         self.prefill_rows = 0
         self.prefill_groups = 0
         self.use_graph, self.check_every, self.allow_compact = use_graph, int(check_every), compact
+        self.ahead = (self.check_every + 1) * self.C  # positions mapped ahead of a host check
         self.compactions = 0
         self.evictions = 0
 
     def run(self) -> List[List[int]]:
         import torch
+
+        if self.C > 1:
+            return self.run_chunk()
 
         from .. import _lib as L
         from ..codec.errors import DecodeDivergenceError
@@ -736,6 +780,214 @@ class SlotDecoder:
             del graph
         return out
 
+    def run_chunk(self) -> List[List[int]]:
+        """:meth:`run` with ``C = chunk`` known tokens per slot and iteration.  The LM forward over a cover does not
+        depend on the coder, so one iteration is: one forward over every live slot's next ``n = min(C, remaining)``
+        tokens (``BatchedGPT2.step_chunk_static``: a slot's K/V pages are read once per C tokens; every logits row the
+        bits of the one-token step), then C ``ns_decode_step`` launches -- launch i over the rows that predict each
+        slot's token i, a slot active while i < n.  Launch 0 reads the ``carry`` row ([S, ld]: what the previous
+        iteration, or the context prefill at admission, predicted), launch i > 0 row i - 1 of the forward's
+        ``[S, C, ld]`` logits (slot stride C * ld); the forward's last row becomes the next carry.  The whole
+        iteration is one captured graph body.  Admission, page mapping (``(check_every + 1) * C`` positions ahead),
+        eviction, compaction and the per-message contexts, qualities and shared pages are those of :meth:`run`."""
+        import torch
+
+        from .. import _lib as L
+        from ..codec.errors import DecodeDivergenceError
+        from ..coder import _bit_rows_to_lists, _ptr, _state_tensor, _stream_handle, _table_registered
+
+        lm, S, N, C = self.lm, self.S, self.N, self.C
+        lens_all = np.asarray([len(t) for t in self.lists], dtype=np.int64)
+        Tcap = max(1, int(lens_all.max(initial=0)))
+        order = np.argsort(-lens_all, kind="stable")  # longest first: the tail is short messages
+        per_ctx = self.contexts is not None
+        if per_ctx:
+            lm.begin_slots(S, 0, Tcap + 1)
+            carry = torch.zeros((S, lm.ld), device=lm.device, dtype=lm.logits_dtype)
+            first = None
+        else:
+            carry = lm.prefill(self.context, S, Tcap + 1)
+            first = lm.first_logits
+        T0 = lm.kv.T0
+        dev = carry.device
+        logits = torch.zeros((S, C, lm.ld), device=dev, dtype=lm.logits_dtype)
+        qual = self.qual
+        P = qual.max_precision if qual is not None else self.ctx.params.precision
+        out_stride = int((Tcap * P + P + 7) // 8 + 8)
+        st = {"tokmat": torch.zeros((S, Tcap), dtype=torch.int32, device=dev),
+              "nlen": torch.zeros(S, dtype=torch.int32, device=dev),
+              "stop": torch.zeros(S, dtype=torch.int32, device=dev),
+              "state": _state_tensor(S, dev),
+              "out_bits": torch.zeros((S, out_stride), dtype=torch.uint8, device=dev)}
+        if per_ctx:
+            st["ctx"] = torch.zeros(S, dtype=torch.int32, device=dev)
+        if qual is not None:
+            st["quality"] = qual.take([0] * S).table(dev)
+        ctx_host = np.full(S, T0, dtype=np.int64)
+        self.ctx.check(L.lib().ns_init_state(self.ctx._h, _ptr(st["state"]), S, _stream_handle()), "ns_init_state")
+        st["state"].view(torch.int32)[:, 7] = L.NS_ST_DONE
+        slot_msg = np.full(S, -1, dtype=np.int64)
+        nlen_host = np.zeros(S, dtype=np.int64)
+        queue = deque(order.tolist())
+        out: List[Optional[List[int]]] = [None] * N
+        init_row = torch.tensor([[0, 1 << P, 0, 0]], dtype=torch.int64, device=dev)
+        p = self.ctx.params
+        k_max = qual.k_max if qual is not None else 0
+        graph, gkey = None, None
+        bufs = {}
+        admit_blocked = False
+        ar = torch.arange(C, device=dev, dtype=torch.int32).unsqueeze(0)
+
+        def body():
+            tix = lm.kv.lens - (st["ctx"] if per_ctx else T0)  # tokens fed = the token the carry row predicts
+            cnt = (st["nlen"] - tix).clamp(0, C)
+            pos = tix.unsqueeze(1) + ar  # [S, C] token indices of the iteration
+            tok = torch.gather(st["tokmat"], 1, pos.clamp(0, Tcap - 1).long()).contiguous()
+            tokT = tok.t().contiguous()  # launch i's tokens, contiguous
+            act = (ar < cnt.unsqueeze(1)).to(torch.uint8).t().contiguous()
+            last = (pos == (st["nlen"] - 1).unsqueeze(1)).to(torch.uint8).t().contiguous()
+            bufs["tok"], bufs["tokT"], bufs["act"], bufs["last"], bufs["cnt"] = tok, tokT, act, last, cnt
+            lm.step_chunk_static(tok, cnt)  # lens += cnt
+            ld_slot = logits.stride(0)
+            with _table_registered(self.ctx, st.get("quality"), k_max):
+                for i in range(C):
+                    rows, ld = (carry, carry.stride(0)) if i == 0 else (logits[:, i - 1], ld_slot)
+                    rc = L.lib().ns_decode_step(self.ctx._h, rows.data_ptr(), ld, st["state"].shape[0],
+                                                _ptr(tokT[i]), _ptr(last[i]), _ptr(act[i]), _ptr(st["state"]),
+                                                _ptr(st["out_bits"]), out_stride, float(p.temp), int(p.topk),
+                                                self.ctx._banned, self.ctx._nbanned, None, 0, _stream_handle())
+                    self.ctx.check(rc, "ns_decode_step")
+            carry.copy_(logits[:, C - 1])  # a slot that fed fewer than C tokens has ended: its carry is not read
+
+        t = 0
+        pipelined = self.use_graph
+        side = torch.cuda.Stream() if pipelined else None
+        pending = None
+        lm.stop_len = None
+        try:
+            while True:
+                if t % self.check_every == 0:
+                    live = slot_msg >= 0
+                    if pipelined:
+                        if pending is not None:
+                            ev, msg_then, fed_then = pending
+                            ev.synchronize()
+                            done = live & (slot_msg == msg_then) & (fed_then >= nlen_host)
+                        else:
+                            ev, done = None, np.zeros(slot_msg.shape, dtype=bool)
+                    else:
+                        ev, done = None, live & ((lm.kv.lens_host - ctx_host) >= nlen_host)
+                    fin = np.nonzero(done)[0]
+                    if fin.size:
+                        if ev is not None:
+                            srows = _rows_after(ev, side, st["state"], fin).numpy()
+                            f = _state_fields(torch.from_numpy(srows))
+                            rows = _rows_after(ev, side, st["out_bits"], fin)
+                        else:
+                            f = _state_fields(st["state"][torch.as_tensor(fin, device=dev)])
+                            rows = st["out_bits"][torch.as_tensor(fin, device=dev)]
+                        bad = fin[(f["flags"] & L.NS_ST_ERR_DIVERGE) != 0]
+                        if bad.size:
+                            raise DecodeDivergenceError(
+                                f"streams {slot_msg[bad].tolist()[:8]}: received token outside the kept top-k")
+                        got = _bit_rows_to_lists(rows, f["bit_pos"])
+                        for j, s in enumerate(fin.tolist()):
+                            out[int(slot_msg[s])] = got[j]
+                        lm.kv.release(fin)
+                        slot_msg[fin] = -1
+                        nlen_host[fin] = 0
+                        admit_blocked = False
+                        fi = torch.as_tensor(fin, device=dev)
+                        st["nlen"][fi] = 0
+                        st["stop"][fi] = 0
+                        live = slot_msg >= 0
+                    empty = np.nonzero(~live)[0]
+                    if queue and empty.size and not admit_blocked:
+                        room = lm.pool.free_pages + lm.pool.growable_pages() - int(live.sum()) - 1
+                        if per_ctx:
+                            adm_m = _admissible(queue, self.contexts, self.ahead - 1, empty.size, room,
+                                                self.keys, self.shares, lm.kv.entries, self.chains,
+                                                lm.kv.prefixes)
+                            if adm_m:
+                                back = self._admit_contexts(st, carry, init_row, empty[:len(adm_m)], adm_m, slot_msg,
+                                                            nlen_host, ctx_host, Tcap)
+                                queue.extendleft(reversed(back))
+                                admit_blocked = bool(back)
+                                live = slot_msg >= 0
+                            if not live.any():
+                                m = queue[0]
+                                raise KVCapacityError(
+                                    f"message {m}: no device memory for the KV pages of its "
+                                    f"{len(self.contexts[m])}-token context")
+                        else:
+                            n_adm = int(min(empty.size, len(queue), max(0, room)))
+                            if n_adm:
+                                adm_s = empty[:n_adm]
+                                adm_m = [queue.popleft() for _ in range(n_adm)]
+                                lm.kv.reset(adm_s)
+                                self._admit(st, carry, first, init_row, adm_s, adm_m, slot_msg, nlen_host, T0, Tcap)
+                                live = slot_msg >= 0
+                    # pages for the next (check_every + 1) * C positions, never past a message's last token
+                    while live.any():
+                        sl = np.nonzero(live)[0]
+                        upto = chunk_page_horizon(lm.kv.lens_host[sl], ctx_host[sl] + nlen_host[sl],
+                                                  self.check_every, C)
+                        if lm.kv.ensure(sl, upto).size == 0:
+                            break
+                        if sl.size == 1:
+                            raise KVCapacityError(f"message {int(slot_msg[sl[0]])} ({int(nlen_host[sl[0]])} tokens) "
+                                                  "needs more KV pages than the device holds")
+                        v = sl[np.argmin(lm.kv.lens_host[sl] - ctx_host[sl])]  # the youngest: fewest tokens fed
+                        queue.appendleft(int(slot_msg[v]))
+                        lm.kv.release([v])
+                        vi = torch.as_tensor([int(v)], device=dev)
+                        st["nlen"][vi] = 0
+                        st["stop"][vi] = 0
+                        slot_msg[v], nlen_host[v] = -1, 0
+                        live = slot_msg >= 0
+                        admit_blocked = True
+                        self.evictions += 1
+                    if not live.any():
+                        break
+                    if self.allow_compact and not queue and int(live.sum()) <= st["state"].shape[0] // 2 and \
+                            st["state"].shape[0] > 1:
+                        keep = np.nonzero(live)[0]
+                        lm.kv.release(np.setdiff1d(np.arange(st["state"].shape[0]), keep))
+                        lm.kv.compact(keep)
+                        lm.B = lm.kv.B
+                        ki = torch.as_tensor(keep, device=dev)
+                        for k in st:
+                            st[k] = st[k].index_select(0, ki).contiguous()
+                        carry = carry.index_select(0, ki).contiguous()
+                        logits = torch.zeros((keep.size, C, lm.ld), device=dev, dtype=lm.logits_dtype)
+                        slot_msg, nlen_host = slot_msg[keep].copy(), nlen_host[keep].copy()
+                        ctx_host = ctx_host[keep].copy()
+                        self.compactions += 1
+                    if pipelined:
+                        ev_now = torch.cuda.Event()
+                        ev_now.record()
+                        pending = (ev_now, slot_msg.copy(), lm.kv.lens_host - ctx_host)
+                key = _layout_key(carry, logits, st["state"], st["tokmat"], lm.kv.table, lm.kv.lens, st.get("ctx"),
+                                  st.get("quality")) + (lm.kv.version,)
+                if self.use_graph:
+                    if graph is None or key != gkey:
+                        graph = None
+                        lm.begin_chunk_static(logits)
+                        graph, gkey = _SlotGraph(body), key
+                    else:
+                        graph.replay()
+                else:
+                    lm.begin_chunk_static(logits)
+                    body()
+                # the host mirror of ``lens += cnt``: a slot of an evicted or finished message has nlen 0 and stays
+                lm.advance_rows(chunk_counts(lm.kv.lens_host - ctx_host, nlen_host, C))
+                t += 1
+        finally:
+            if graph is not None:
+                torch.cuda.current_stream().synchronize()
+            del graph
+        return out
+
     def _admit_contexts(self, st, logits, init_row, slots, msgs, slot_msg, nlen_host, ctx_host, Tcap):
         """Admit ``msgs`` with their own contexts into ``slots``: pages for each context and the message's first
         positions, one ragged prefill into those pages, then the slot state of :meth:`_admit` with a per-slot context
@@ -748,7 +1000,7 @@ class SlotDecoder:
         nl = np.asarray([len(self.lists[m]) for m in msgs], dtype=np.int64)
         chains = [self.chains[m] for m in msgs] if self.chains is not None else None
         ok = _map_contexts(lm.kv, slots, [self.keys[m] for m in msgs], [self.shares[m] for m in msgs], tl,
-                           tl + np.minimum(self.check_every + 1, nl), chains)
+                           tl + np.minimum(self.ahead, nl), chains)
         back = [m for m, k in zip(msgs, ok) if not k]
         slots, msgs, tl = slots[ok], [m for m, k in zip(msgs, ok) if k], tl[ok]
         if not msgs:

@@ -116,9 +116,22 @@ def _encode_streams(lm, bit_lists: List[List[int]], context: List[int], quality)
     return [lm.encode_arithmetic(bits, context, quality=_q_at(quality, i)) for i, bits in enumerate(bit_lists)]
 
 
-def _decode_streams(lm, spans: List[List[int]], context: List[int], quality) -> List[List[int]]:
+def _chunk_kw(lm, chunk: int) -> dict:
+    """``chunk=`` for a provider's ``decode_batch`` (several known tokens per LM forward); 1 passes nothing on."""
+    if isinstance(chunk, bool) or not isinstance(chunk, int) or not 1 <= chunk <= 16:
+        raise ValueError(f"chunk must be an int in 1..16, got {chunk!r}")
+    if chunk == 1:
+        return {}
+    if not _takes(getattr(lm, "decode_batch", None), "chunk"):
+        raise ValueError("chunk > 1 needs a provider whose decode_batch takes chunk= (the native GPT-2 provider)")
+    return {"chunk": chunk}
+
+
+def _decode_streams(lm, spans: List[List[int]], context: List[int], quality, chunk: int = 1) -> List[List[int]]:
+    ckw = _chunk_kw(lm, chunk)
     kw = _qkw(getattr(lm, "decode_batch", None), quality) if hasattr(lm, "decode_batch") else None
     if kw is not None:
+        kw = dict(kw, **ckw)
         if getattr(lm, "decodes_without_state", False):
             # the arithmetic coder decodes from the tokens alone: drop the queued states to stay aligned
             queue = getattr(lm, "_decode_states", None)
@@ -140,10 +153,13 @@ def _encode_streams_each(lm, bit_lists: List[List[int]], contexts: List[List[int
             for i, (bits, ctx) in enumerate(zip(bit_lists, contexts))]
 
 
-def _decode_streams_each(lm, spans: List[List[int]], contexts: List[List[int]], quality) -> List[List[int]]:
+def _decode_streams_each(lm, spans: List[List[int]], contexts: List[List[int]], quality,
+                         chunk: int = 1) -> List[List[int]]:
     """``_decode_streams`` with one context per span (``seed_texts``)."""
+    ckw = _chunk_kw(lm, chunk)
     kw = _qkw(getattr(lm, "decode_batch", None), quality) if _takes_contexts(getattr(lm, "decode_batch", None)) else None
     if kw is not None:
+        kw = dict(kw, **ckw)
         if getattr(lm, "decodes_without_state", False):
             queue = getattr(lm, "_decode_states", None)
             if queue:
@@ -268,11 +284,14 @@ def _assemble(packets: List[Packet]) -> bytes:
 def stego_decode_batch(span_sets: Sequence[Iterable[List[int]]], *, use_crc: bool = True, ecc: Optional[str] = "rs",
                        nsym: int = 10, quality: Optional[Dict[str, float]] = None,
                        qualities: Optional[Sequence[Optional[Dict[str, float]]]] = None, seed_text: str = "",
-                       seed_texts: Optional[Sequence[str]] = None, lm, return_errors: bool = False) -> List[Any]:
+                       seed_texts: Optional[Sequence[str]] = None, lm, return_errors: bool = False,
+                       chunk: int = 1) -> List[Any]:
     """Every message's spans -> its bytes, all spans decoded as one batch.  Errors (missing chunks, CRC, RS,
     cfg mismatch) raise for the first failing message, or are returned in its slot with
     ``return_errors=True``.  ``seed_texts``: one seed text per message, ``qualities``: one quality per message, as
-    in :func:`stego_encode_batch`."""
+    in :func:`stego_encode_batch`.  ``chunk`` (1..16, default 1): known cover tokens per LM forward, passed to the
+    provider's ``decode_batch`` (the same bits, fewer passes over the KV pages); ``ValueError`` outside 1..16 or
+    with a provider that has no chunked decode."""
     span_sets = list(span_sets)
     per_msg = _seed_contexts(lm, seed_texts, len(span_sets)) if seed_texts is not None else None
     mode = normalise_ecc(ecc)
@@ -287,10 +306,10 @@ def stego_decode_batch(span_sets: Sequence[Iterable[List[int]]], *, use_crc: boo
     if per_q is not None:
         q = [per_q[mi] for mi in owner]
     if per_msg is not None:
-        bits = _decode_streams_each(lm, flat, [per_msg[mi] for mi in owner], q) if flat else []
+        bits = _decode_streams_each(lm, flat, [per_msg[mi] for mi in owner], q, chunk) if flat else []
     else:
         context = list(lm.encode_seed(seed_text))
-        bits = _decode_streams(lm, flat, context, q) if flat else []
+        bits = _decode_streams(lm, flat, context, q, chunk) if flat else []
     packets: List[List[Packet]] = [[] for _ in span_sets]
     errors: List[Optional[Exception]] = [None] * len(span_sets)
     for mi, b in zip(owner, bits):
