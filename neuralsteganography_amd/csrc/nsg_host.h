@@ -10,20 +10,18 @@
 
 namespace nsg {
 
-// per-stream statistics of the wide path's first pass
+// per-stream row statistics of the wide path (wide_onepass_kernel; the rank coder: wide_stats_kernel / rank64_prep_kernel)
 struct WideStat {
     float m;          // row max (valid ids)
-    float m2;         // second largest value (>= 2 ids are always collected)
+    float m2;         // second largest value (rank coder; the one-pass kernel finds it only when it needs it)
     float r;          // reference of the fast sum
     uint32_t active;  // 0: stream done/inactive this step
     double S_lo;      // proven interval of the canonical float64 row sum
     double S_hi;
     double S_fast;
     uint32_t exact;   // 1: the fast bound is unusable, the CDF kernel computes the exact sum
-    uint32_t pad;
+    uint32_t pad;     // 1: the one-pass kernel's overflow sweep left this stream's keys to the device-wide sort
     double S_r, B_r, U_r;  // raw streaming sums against r (statistics: row_stats_from_stream)
-    float xt;         // wide_stream_kernel: final collection threshold (segment entries below it are stale)
-    uint32_t nraw;    // wide_stream_kernel: entries written to the stream's segment
 };
 
 }  // namespace nsg

@@ -4,14 +4,19 @@
 // and the oracle.
 //
 // Coder step (ns_encode_step / ns_decode_step / ns_sample_step with K > the single-pass limit):
-//   1. wide_scan_kernel    (512 threads/stream): pass 1 over the row -> max, second max, fast-sum interval;
-//                          pass 2 -> every id that can clear the 1/R cutoff, plus the top two, as 49-bit
-//                          (value desc, id asc) keys in LDS; <= 5,632 keys: LDS sort + the canonical tail
-//                          (fast_tail).  Other streams: keys to global memory, stream id onto a work list.
-//   2. rocprim::segmented_radix_sort_keys_desc : descending sort of the listed streams' keys (> 5,632 keys)
-//   3. wide_cdf_kernel     (1024 threads/block, over the work list): cutoff, canonical sums (the exact row sum
-//                          when the fast-sum interval is ambiguous), rint, int64 scan, overfill, selection,
-//                          interval update
+//   1. wide_onepass_kernel (512 threads/stream, two workgroups per CU): streams the row once -> max, fast-sum
+//                          interval, and every id that can clear the 1/R cutoff as raw (value, id) entries in
+//                          per-wave LDS buffers; <= 6,144 kept keys: LDS sort + the canonical tail (fast_tail,
+//                          the exact row sum included) finish the step in the same workgroup.  A wave buffer
+//                          that overflows: one more block sweep collects the keys into global memory; more
+//                          than 6,144 of them, or a step fast_tail hands on (sampler, statistics fallback,
+//                          errors): stream id onto a work list.
+//   2. wide_offsets_kernel + rocprim::segmented_radix_sort_keys_desc : descending sort of the 49-bit (value
+//                          desc, id asc) keys of the streams with more than 6,144; empty segments for the rest
+//                          (fast_tail hands its streams on with their keys already in rank order)
+//   3. wide_cdf_kernel     (1024 threads/block, grid-stride over the work list): the general canonical tail --
+//                          cutoff, canonical sums (the exact row sum when the fast-sum interval is ambiguous),
+//                          rint, int64 scan, overfill, selection, interval update
 // Rank coder (ns_rank_*_step): wide_stats_kernel (wave per stream) -> wide_collect_kernel (blocks per chunk,
 // every valid id) -> the device-wide sort -> wide_rank_kernel.
 // An id left out of the collection has e_i < S_lo/R <= S/R, i.e. p_i < 1/R for certain, so the first rank
@@ -19,7 +24,6 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
@@ -41,7 +45,7 @@ __device__ __forceinline__ uint64_t wkey(float x, uint32_t j) {
 __device__ __forceinline__ uint32_t wkey_id(uint64_t k) { return 0x1FFFFu - (uint32_t)(k & 0x1FFFFu); }
 __device__ __forceinline__ float wkey_val(uint64_t k) { return unord32((uint32_t)(k >> 17)); }
 
-// ------------------------------------------------------------------------------------------ pass 1
+// ------------------------------------------------------------------------------------------ row statistics (rank coder)
 template <typename T, bool DECODE>
 __global__ __launch_bounds__(WPB* WAVE) void wide_stats_kernel(StepParams p, WideStat* ws, unsigned int* count) {
     constexpr int W = Elem<T>::W;
@@ -141,7 +145,7 @@ __global__ __launch_bounds__(WPB* WAVE) void wide_stats_kernel(StepParams p, Wid
     }
 }
 
-// ------------------------------------------------------------------------------------------ pass 2
+// ------------------------------------------------------------------------------------------ key collection (rank coder)
 template <typename T>
 __global__ __launch_bounds__(256) void wide_collect_kernel(StepParams p, const WideStat* ws, uint64_t* keys,
                                                            unsigned int* count, int cap) {
@@ -222,13 +226,11 @@ __global__ __launch_bounds__(256) void wide_collect_kernel(StepParams p, const W
     }
 }
 
-// segments for the device-wide sort: only the streams with more than `small` keys (the rest are sorted in LDS by
-// wide_fast_kernel; small = 0 sorts every segment)
+// segments for the device-wide sort: only the streams with more than `small` keys (the rest were sorted in LDS by
+// wide_onepass_kernel's fast_tail; small = 0, the rank coder, sorts every segment)
 __global__ void wide_offsets_kernel(int B, int cap, const WideStat* ws, const unsigned int* count,
-                                    unsigned int* begin, unsigned int* end, unsigned int small,
-                                    unsigned int* todo) {
+                                    unsigned int* begin, unsigned int* end, unsigned int small) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (todo && b == 0) todo[0] = 0u;
     if (b < B) {
         const unsigned int n = ws[b].active ? count[b] : 0u;
         begin[b] = (unsigned int)(b * cap);
@@ -237,7 +239,7 @@ __global__ void wide_offsets_kernel(int B, int cap, const WideStat* ws, const un
     }
 }
 
-// ------------------------------------------------------------------------------------------ pass 4
+// ------------------------------------------------------------------------------------------ canonical tail (list kernel)
 // the next P payload bits (LSB-first bytes) as an MSB-first integer, zero-padded past the end: one bit per lane
 // and a ballot (every lane of the wave must be active); the loads are independent, not a P-long chain
 __device__ __forceinline__ uint64_t payload_window(const StepParams& p, int b, int64_t bit_pos) {
@@ -721,7 +723,7 @@ __device__ __forceinline__ void wide_cdf_stream(const StepParams& p, const WideS
                         want_stats);
 }
 
-// the streams wide_fast_kernel listed (todo[1 .. todo[0]]: more keys than its LDS holds, or a step it hands on),
+// the streams wide_onepass_kernel listed (todo[1 .. todo[0]]: more keys than its LDS holds, or a step it hands on),
 // a grid-stride loop over the list so that the launch does not depend on how many there are
 template <typename T, bool DECODE>
 __global__ __launch_bounds__(WIDE_THREADS) void wide_cdf_kernel(StepParams p, const WideStat* ws,
@@ -735,26 +737,17 @@ __global__ __launch_bounds__(WIDE_THREADS) void wide_cdf_kernel(StepParams p, co
     }
 }
 
-// ------------------------------------------------------------------------------------------ passes 3+4 in LDS
+// ------------------------------------------------------------------------------------------ LDS sort + canonical tail
 // The usual stream keeps a few thousand ids (3·N(0,1) logits at precision 16: 2-5k), far fewer than the
 // device-wide sort is sized for.  One 512-thread workgroup per such stream (count <= FAST_NL) sorts its keys in
 // LDS -- a counting sort on FAST_NB key-range buckets, then each key's rank inside its bucket by counting the
 // larger bucket-mates (a bitonic sort instead when a bucket holds more than FAST_OCC_MAX keys) -- and runs the
-// canonical tail on the sorted keys: the same arithmetic, in the same order, as wide_cdf_kernel.  Streams that
-// need the exact row sum, the row-statistics fallback, the sampler, or hit an error are handed to
-// wide_cdf_kernel (listed in todo) with their sorted keys written to keys_out; streams with more keys were
+// canonical tail on the sorted keys: the same arithmetic, in the same order, as wide_cdf_kernel, the exact row
+// sum included.  Streams that need the row-statistics fallback or the sampler, or hit an error, are handed to
+// wide_cdf_kernel (listed in todo) with their sorted keys written to keys_out; streams with more keys are
 // sorted by the device-wide sort and are listed too.  Round 3-4: 53,248 B of LDS and <= 80 VGPRs, three
 // workgroups per CU (measured 0.53 vs 0.58 ms per step with 8,192 keys / 3,840 buckets at two per CU, an older
 // kernel); round 5: two per CU without the spill frame (NSG_FAST_WAVES_PER_SIMD below).
-#ifndef NSG_SCAN_DIAG
-#define NSG_SCAN_DIAG 0
-#endif
-#ifndef NSG_SCAN_VEC_BYTES
-#define NSG_SCAN_VEC_BYTES 64  // row bytes per thread per group in the two sweeps (two groups in flight)
-#endif
-#ifndef NSG_SCAN_P1_KEEP
-#define NSG_SCAN_P1_KEEP 1  // pass 1 loads with the default policy (0: non-temporal, for A/B timing)
-#endif
 constexpr int FAST_THREADS = 512;
 constexpr int FAST_WAVES = FAST_THREADS / WAVE;
 #ifndef NSG_FAST_NL
@@ -786,24 +779,15 @@ __device__ __forceinline__ int wave_min_int(int v) {
 }
 
 // the LDS path for one stream whose n <= FAST_NL collected keys sit at `kin` (global or LDS, any order): sort,
-// then the canonical tail; every thread of the 512-thread block calls it
-// the keys a thread loads: slot r of thread tid -- any partition of the stream's n keys over the block's slots
-// (the counting sort below does not care which thread holds which key)
-struct KeysFlat {  // one array (global memory or LDS): slot r of thread tid = key r * FAST_THREADS + tid
-    const uint64_t* k;
-    int n;
-    __device__ __forceinline__ bool operator()(int r, uint64_t& key) const {
-        const int i = r * FAST_THREADS + (int)threadIdx.x;
-        key = i < n ? k[i] : 0ull;
-        return i < n;
-    }
-};
-// INX: the exact row sum (forced, unusable bound, or an ambiguous cutoff) is computed here by the block,
-// instead of handing the stream to the list kernel (the one-pass kernel: ~1 % of stream-steps)
-template <typename T, bool DECODE, bool INX = false, typename KeyAt>
-__device__ __forceinline__ void fast_tail(const StepParams& p, const WideStat& w, WideStat* wsb, const int b,
-                                          const int n, const KeyAt kin, uint64_t* keys_out, const int cap,
-                                          unsigned int* todo, uint64_t* s_keys, uint64_t* s_aux) {
+// then the canonical tail; every thread of the 512-thread block calls it.
+// kin(r, key) gives the keys a thread loads: slot r of thread tid -- any partition of the stream's n keys over the
+// block's slots (the counting sort below does not care which thread holds which key).
+// The exact row sum (forced, unusable bound, or an ambiguous cutoff: ~1 % of stream-steps) is computed here by
+// the block, not handed to the list kernel.
+template <typename T, bool DECODE, typename KeyAt>
+__device__ __forceinline__ void fast_tail(const StepParams& p, const WideStat& w, const int b, const int n,
+                                          const KeyAt kin, uint64_t* keys_out, const int cap, unsigned int* todo,
+                                          uint64_t* s_keys, uint64_t* s_aux) {
     uint32_t* s_cnt = (uint32_t*)s_aux;
     const int tid = (int)threadIdx.x, lane = tid & (WAVE - 1), wv = tid / WAVE;
     // ---- load (unsorted, as collected) + key range; every key is in registers before the first LDS write
@@ -951,10 +935,6 @@ __device__ __forceinline__ void fast_tail(const StepParams& p, const WideStat& w
     }
     const uint64_t top = s_keys[0];
     __syncthreads();
-#if NSG_SCAN_DIAG == 3  // passes 1 and 2 and the LDS sort only
-    if (tid == 0) atomicExch((unsigned int*)&keys_out[(int64_t)b * cap], (unsigned int)ks[0]);  // keep ks live
-    return;
-#endif
     auto defer = [&]() __attribute__((always_inline)) {  // hand the stream to wide_cdf_kernel with its keys in rank order
         uint64_t* ko = keys_out + (int64_t)b * cap;
 #pragma unroll
@@ -968,7 +948,7 @@ __device__ __forceinline__ void fast_tail(const StepParams& p, const WideStat& w
     const double m = (double)wkey_val(top);
     const bool want_stats = !DECODE && p.stats != nullptr;
     RowStats rs{0.0, 0.0, 0.0};
-    if ((!DECODE && p.sample) || (w.exact && !INX) ||
+    if ((!DECODE && p.sample) ||
         (want_stats && !row_stats_from_stream(w.S_r, w.B_r, w.U_r, w.r, m, p.inv_temp, rs))) {
         defer();
         return;
@@ -1011,7 +991,7 @@ __device__ __forceinline__ void fast_tail(const StepParams& p, const WideStat& w
         fb = min(fb, s_i[i]);
         fa = min(fa, s_i[FAST_WAVES + i]);
     }
-    if (INX && (exact || fa < fb)) {
+    if (exact || fa < fb) {
         // the canonical exact row sum by this block (s_keys is scratch: e_i are recomputed from the registers)
         __syncthreads();
         const char* rowc = (const char*)p.logits + (int64_t)b * p.ld * (int64_t)sizeof(T);
@@ -1036,18 +1016,11 @@ __device__ __forceinline__ void fast_tail(const StepParams& p, const WideStat& w
         fa = Kc;
     }
     NSG_STAMP(p, b, tid, 6);
-#if NSG_SCAN_DIAG == 4  // timing diagnostics: up to the cutoff
-    if (tid == 0) atomicExch((unsigned int*)&keys_out[(int64_t)b * cap], (unsigned int)(fb + fa));
-    return;
-#endif
     int k = fb < 2 ? 2 : fb;
     if (k > p.topk) k = p.topk;
-    // ambiguous cutoff (the exact row sum: measured cheaper in the list kernel than in this one, whose
-    // workgroup slots are the row stream's) or a degenerate row: wide_cdf_kernel
-    if (fa < fb || k > Kc) {
-        // an ambiguous cutoff is marked exact, so wide_cdf_kernel goes straight to the exact row sum (it would
-        // find the same ambiguity first)
-        if (fa < fb && tid == 0) wsb->exact = 1u;
+    // a degenerate row (fewer than two keys): wide_cdf_kernel.  An ambiguous cutoff (fa < fb) was settled by the
+    // exact row sum above.
+    if (k > Kc) {
         defer();
         return;
     }
@@ -1180,16 +1153,30 @@ __device__ __forceinline__ void fast_tail(const StepParams& p, const WideStat& w
     NSG_STAMP_RT(p, b, tid, 10);
 }
 
+// ------------------------------------------------------------------------------------------ one-pass wide step
+// The row is streamed ONCE.  The collection threshold x_t = r + T ln(S_r / R) (an id below it has e_i < S/R:
+// below the cutoff for certain) depends on the row sum S, known only after a whole sweep.  But any partial sum is
+// a lower bound of S, so a threshold computed from the ids seen so far is a valid (lower, i.e. collect-more)
+// threshold, and it only rises as the sweep goes on:
+//   * each of the 8 waves takes a contiguous slice of the row; its last NSW tiles (8 x NSW x 1 KiB = 4,096 ids,
+//     a stratified sample) are read first; their max is the reference r and their sum the first threshold;
+//   * the wave streams the rest of its slice (non-temporal 16-B loads, a ring of NR tiles refilled in place),
+//     accumulating the fast sum (fp32 per tile, float64 across tiles), e * |arg| for the data-dependent bound,
+//     the lane's max, and appending the ids at or above its threshold to its own LDS buffer
+//     (OP_CAPW keys; when full, compacted to the current threshold -- ids below it are below the final one too);
+//   * after every ring group the wave publishes its partial sum and re-reads the others' (plain LDS words:
+//     each is a partial sum, so whatever subset is read is a lower bound), and raises its threshold.
+// At the end the buffers are filtered to x >= x_t(final interval) -- exactly a prefix of the ranking -- and handed
+// to fast_tail.  k >= 2 needs the row's top two: when fewer than two ids clear the threshold (a peaked row) a block
+// rescan finds the second largest value and a sweep collects down to it.  A wave whose buffer overflows even after
+// compaction makes the stream take one more block sweep that collects into global memory (sorted in LDS by
+// fast_tail when it fits, else by the device-wide sort and the list kernel).
+#ifndef NSG_OP_RING
+#define NSG_OP_RING 4
+#endif
+constexpr int OP_CAPW = FAST_NL / FAST_WAVES;  // keys per wave buffer
 
-// ------------------------------------------------------------------------------------------ fused wide step
-// One 512-thread workgroup per stream does passes 1 and 2 and, for the usual stream, the whole step:
-//   pass 1: stream the row once (default cache policy) -> max, second max, the proven fast-sum interval
-//           (fp32 groups of W terms, as wide_stats_kernel: the same bound)
-//   pass 2: stream it again -- three workgroups per CU keep ~768 rows (~155 MB fp32) in flight, within the
-//           256 MiB Infinity Cache, so the re-read can be served there (a non-temporal pass 1 measured 4 % slower
-//           overall) -- collecting the ids that can clear the cutoff into LDS
-//   then fast_tail (LDS sort + canonical tail).  More than FAST_NL keys: pass 3 writes them to keys_in for the
-//   device-wide sort and the stream is listed for wide_cdf_kernel.
+// a wave-uniform value the compiler cannot prove uniform, moved to scalar registers
 __device__ __forceinline__ float uni_f32(float v) {
     return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
 }
@@ -1199,297 +1186,6 @@ __device__ __forceinline__ double uni_f64(double v) {
     const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(u >> 32));
     return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
 }
-
-template <typename T, bool DECODE>
-__global__ __launch_bounds__(FAST_THREADS, NSG_FAST_WAVES_PER_SIMD) void wide_scan_kernel(StepParams p, WideStat* ws, uint64_t* keys_in,
-                                                                   uint64_t* keys_out, unsigned int* count, int cap,
-                                                                   unsigned int* todo) {
-    __shared__ uint64_t s_keys[FAST_NL];
-    __shared__ uint64_t s_aux[FAST_NB / 2];
-    constexpr int W = Elem<T>::W;
-    constexpr int G = NSG_SCAN_VEC_BYTES / (4 * W);  // 16-B vectors per thread per block row group
-    constexpr int TS = FAST_THREADS * W;      // ids per block-wide vector row
-    const int b = blockIdx.x, tid = (int)threadIdx.x, lane = tid & (WAVE - 1), wv = tid / WAVE;
-    const ns_stream_state st = p.state[b];
-    bool active = !(st.flags & NS_ST_DONE);
-    if (!DECODE && !p.sample && active && st.bit_pos >= p.nbits[b]) {
-        if (tid == 0 && !(p.flags & NS_STEP_FINISH_SENT)) p.state[b].flags = st.flags | NS_ST_DONE;
-        active = false;
-    }
-    if (DECODE && p.active && !p.active[b]) active = false;
-    if (!active) {
-        if (tid == 0) {
-            ws[b].active = 0;
-            count[b] = 0;
-        }
-        return;
-    }
-    const int V = p.V;
-    const char* rowc = (const char*)p.logits + (int64_t)b * p.ld * (int64_t)sizeof(T);
-    const RowReader rd(rowc, (uint32_t)(p.ld * (int64_t)sizeof(T)));
-    const int nvec = (V + W - 1) / W;
-    const int nsup = (nvec + G * FAST_THREADS - 1) / (G * FAST_THREADS);
-    // x[g][.] = block-row (s*G + g) of this thread; ids >= V and banned ids -> `fill` (pass 1: -inf, which adds
-    // nothing to the sums; pass 2: NaN, which no threshold collects -- a real -inf logit is a valid id and is
-    // collected when the threshold is -inf, as in wide_collect_kernel)
-    auto fetch = [&](int sI, uint4 (&raw)[G], bool keep) __attribute__((always_inline)) {
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            const int v = (sI * G + g) * FAST_THREADS + tid;
-            raw[g] = keep ? rd.vec_keep(v) : rd.vec(v);
-        }
-    };
-    auto prep = [&](int sI, const uint4 (&raw)[G], float (&x)[G][W], int& bi, int& next_ban,
-                    float fill) __attribute__((always_inline)) {
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            Elem<T>::unpack(raw[g], x[g]);
-            const int j0 = ((sI * G + g) * FAST_THREADS + tid) * W;
-#pragma unroll
-            for (int q = 0; q < W; ++q)
-                if (j0 + q >= V) x[g][q] = fill;
-            while (next_ban < (sI * G + g + 1) * TS) {
-#pragma unroll
-                for (int q = 0; q < W; ++q)
-                    if (j0 + q == next_ban) x[g][q] = fill;
-                ++bi;
-                next_ban = bi < p.nbanned ? p.banned[bi] : 0x7FFFFFFF;
-            }
-        }
-    };
-    // one sweep over the row: consume(sI, x) for every block row in order, the loads of block row sI + 1 in
-    // flight while block row sI is consumed (two register buffers, no copies between them)
-    auto sweep = [&](bool keep, float fill, auto&& consume) __attribute__((always_inline)) {
-        int bi = 0, next_ban = p.nbanned > 0 ? p.banned[0] : 0x7FFFFFFF;
-        uint4 ra[G], rb[G];
-        fetch(0, ra, keep);
-        for (int sI = 0; sI < nsup; sI += 2) {
-            if (sI + 1 < nsup) fetch(sI + 1, rb, keep);
-            {
-                float x[G][W];
-                prep(sI, ra, x, bi, next_ban, fill);
-                consume(sI, x);
-            }
-            if (sI + 1 < nsup) {
-                if (sI + 2 < nsup) fetch(sI + 2, ra, keep);
-                float x[G][W];
-                prep(sI + 1, rb, x, bi, next_ban, fill);
-                consume(sI + 1, x);
-            }
-        }
-    };
-    // ---- pass 1
-    float r = 0.0f, m1 = -__builtin_inff(), m2 = -__builtin_inff();
-    double acc64 = 0.0, b64 = 0.0, u64 = 0.0;
-    const bool stats = p.stats != nullptr;
-    sweep(NSG_SCAN_P1_KEEP != 0, -__builtin_inff(), [&](int sI, float (&x)[G][W]) __attribute__((always_inline)) {
-        if (sI == 0) {  // reference r = max of the first block rows (any finite reference is valid)
-            float mx = -__builtin_inff();
-#pragma unroll
-            for (int g = 0; g < G; ++g)
-#pragma unroll
-                for (int q = 0; q < W; ++q) mx = fmaxf(mx, x[g][q]);
-            mx = wave_max(mx);
-            float* s_f = (float*)(s_aux + 8);
-            if (lane == 0) s_f[wv] = mx;
-            __syncthreads();
-            r = s_f[0];
-#pragma unroll
-            for (int i = 1; i < FAST_WAVES; ++i) r = fmaxf(r, s_f[i]);
-            if (r == -__builtin_inff()) r = 0.0f;
-        }
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            float a = 0.0f, bb = 0.0f, uu = 0.0f;
-#pragma unroll
-            for (int q = 0; q < W; ++q) {
-                const float dx = fmaxf(x[g][q] - r, -3.0e38f);
-                const float e = __builtin_amdgcn_exp2f(dx * p.c32);
-                a += e;
-                if (stats) {
-                    bb += e * dx;
-                    uu += __builtin_amdgcn_exp2f(dx * L2E_F);
-                }
-                m2 = fmaxf(m2, fminf(m1, x[g][q]));
-                m1 = fmaxf(m1, x[g][q]);
-            }
-            acc64 += (double)a;
-            b64 += (double)bb;
-            u64 += (double)uu;
-        }
-    });
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const float o1 = __shfl_xor(m1, off), o2 = __shfl_xor(m2, off);
-        m2 = fmaxf(fminf(m1, o1), fmaxf(m2, o2));
-        m1 = fmaxf(m1, o1);
-    }
-    acc64 = wave_sum_butterfly(acc64);
-    b64 = wave_sum_butterfly(b64);
-    u64 = wave_sum_butterfly(u64);
-    {
-        double* s_d = (double*)(s_aux + 16);  // [3][FAST_WAVES]
-        float* s_f = (float*)(s_aux + 48);    // [2][FAST_WAVES]
-        if (lane == 0) {
-            s_d[wv] = acc64;
-            s_d[FAST_WAVES + wv] = b64;
-            s_d[2 * FAST_WAVES + wv] = u64;
-            s_f[wv] = m1;
-            s_f[FAST_WAVES + wv] = m2;
-        }
-        __syncthreads();
-        acc64 = b64 = u64 = 0.0;
-        m1 = m2 = -__builtin_inff();
-#pragma unroll
-        for (int i = 0; i < FAST_WAVES; ++i) {
-            acc64 += s_d[i];
-            b64 += s_d[FAST_WAVES + i];
-            u64 += s_d[2 * FAST_WAVES + i];
-            const float o1 = s_f[i], o2 = s_f[FAST_WAVES + i];
-            m2 = fmaxf(fminf(m1, o1), fmaxf(m2, o2));
-            m1 = fmaxf(m1, o1);
-        }
-    }
-    // block-uniform from here on: into scalar registers (the LDS tail needs the vector registers)
-    acc64 = uni_f64(acc64);
-    b64 = uni_f64(b64);
-    u64 = uni_f64(u64);
-    m1 = uni_f32(m1);
-    m2 = uni_f32(m2);
-    WideStat w;
-    {
-        double Sf = 0.0, S_lo = 0.0, S_hi = 0.0;
-        const bool ok = fast_sum_interval(acc64, r, (double)(m1 + 0.0f), p.c32, p.inv_temp, W, Sf, S_lo, S_hi);
-        w.m = m1;
-        w.m2 = m2;
-        w.r = r;
-        w.active = 1;
-        w.S_lo = S_lo;
-        w.S_hi = S_hi;
-        w.S_fast = Sf;
-        w.exact = (ok && !(p.flags & NS_STEP_FORCE_EXACT_SUM)) ? 0u : 1u;
-        w.pad = 0;
-        w.S_r = acc64;
-        w.B_r = b64;
-        w.U_r = u64;
-        w.S_lo = uni_f64(w.S_lo);
-        w.S_hi = uni_f64(w.S_hi);
-        w.S_fast = uni_f64(w.S_fast);
-        w.exact = (uint32_t)__builtin_amdgcn_readfirstlane((int)w.exact);
-    }
-    if (tid == 0) ws[b] = w;
-#if NSG_SCAN_DIAG == 1  // timing diagnostics (tools/wide_timing.py on a tools/build_variant.sh build): pass 1 only
-    if (tid == 0) count[b] = 0u;
-    return;
-#endif
-    // ---- collection threshold (as wide_collect_kernel)
-    float xt;
-    {
-        const double thr = 1.0 / (double)(st.hi - st.lo);
-        const double temp = 1.0 / p.inv_temp;
-        if (p.sample) {
-            const double t = (double)w.m - temp * 41.58883083359672;
-            xt = (float)(t - 1.0e-4 * (1.0 + fabs((double)w.m) + temp * 41.58883083359672));
-        } else if (w.exact) {
-            xt = -__builtin_inff();
-        } else {
-            const double L = log(w.S_lo * thr);
-            const double t = (double)w.m + temp * L;
-            xt = (float)(t - 1.0e-4 * (1.0 + fabs((double)w.m) + fabs(temp * L)));
-        }
-        xt = uni_f32(fminf(xt, w.m2));  // at least the top two ids (k >= 2)
-    }
-    // ---- pass 2 (and pass 3 into global memory when the keys overflow the LDS)
-    uint32_t* s_ctr = (uint32_t*)(s_aux + FAST_NB / 2 - 1);
-    if (tid == 0) s_ctr[0] = 0u;
-    __syncthreads();
-    auto collect = [&](bool to_global) __attribute__((always_inline)) {
-        uint64_t* kout = keys_in + (int64_t)b * cap;
-        sweep(false, __builtin_nanf(""), [&](int sI, float (&x)[G][W]) __attribute__((always_inline)) {
-            uint32_t tot = 0;
-#pragma unroll
-            for (int g = 0; g < G; ++g)
-#pragma unroll
-                for (int q = 0; q < W; ++q) tot += (uint32_t)popc64(ballot(x[g][q] >= xt));
-            if (tot == 0u) return;  // wave-uniform
-            uint32_t base = 0u;
-            if (lane == 0) base = atomicAdd(s_ctr, tot);
-            base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-            uint32_t off = 0u;
-#pragma unroll
-            for (int g = 0; g < G; ++g) {
-                const int j0 = ((sI * G + g) * FAST_THREADS + tid) * W;
-#pragma unroll
-                for (int q = 0; q < W; ++q) {
-                    const uint64_t mk = ballot(x[g][q] >= xt);  // recomputed: cheaper than holding G*W masks
-                    const uint32_t pos = base + off + (uint32_t)lanes_below(mk);
-                    if ((mk >> lane) & 1ull) {
-                        const uint64_t key = wkey(x[g][q], (uint32_t)(j0 + q));
-                        if (to_global) {
-                            if (pos < (uint32_t)cap) kout[pos] = key;  // n <= V - nbanned <= cap
-                        } else if (pos < (uint32_t)FAST_NL) {
-                            s_keys[pos] = key;
-                        }
-                    }
-                    off += (uint32_t)popc64(mk);
-                }
-            }
-        });
-    };
-    collect(false);
-    __syncthreads();
-    const int n = (int)s_ctr[0];
-#if NSG_SCAN_DIAG == 2  // passes 1 and 2 only
-    if (tid == 0) count[b] = 0u;
-    return;
-#endif
-    if (n <= FAST_NL) {
-        if (tid == 0) count[b] = (unsigned int)n;
-        fast_tail<T, DECODE>(p, w, &ws[b], b, n, KeysFlat{s_keys, n}, keys_out, cap, todo, s_keys, s_aux);
-        return;
-    }
-    __syncthreads();
-    if (tid == 0) s_ctr[0] = 0u;
-    __syncthreads();
-    collect(true);
-    if (tid == 0) {
-        count[b] = (unsigned int)n;
-        todo[1 + atomicAdd(&todo[0], 1u)] = (unsigned int)b;
-    }
-}
-
-// ------------------------------------------------------------------------------------------ one-pass wide step
-// (round 3) The row is streamed ONCE.  wide_scan_kernel needed two sweeps because the collection threshold
-// x_t = r + T ln(S_r / R) (an id below it has e_i < S/R: below the cutoff for certain) depends on the row sum S,
-// known only after the first sweep.  But any partial sum is a lower bound of S, so a threshold computed from the
-// ids seen so far is a valid (lower, i.e. collect-more) threshold, and it only rises as the sweep goes on:
-//   * each of the 8 waves takes a contiguous slice of the row; its last NSW tiles (8 x NSW x 1 KiB = 4,096 ids,
-//     a stratified sample) are read first; their max is the reference r and their sum the first threshold;
-//   * the wave streams the rest of its slice (non-temporal 16-B loads, a ring of NR tiles refilled in place),
-//     accumulating the fast sum (fp32 per tile, float64 across tiles), e * |arg| for the data-dependent bound,
-//     the lane's top two values, and appending the ids at or above its threshold to its own LDS buffer
-//     (704 keys; when full, compacted to the current threshold -- ids below it are below the final one too);
-//   * after every ring group the wave publishes its partial sum and re-reads the others' (plain LDS words:
-//     each is a partial sum, so whatever subset is read is a lower bound), and raises its threshold;
-//   * ids that can be among the top two are kept too (k >= 2): a wave's threshold is min(x_t, its running
-//     second max), which never exceeds the row's second max when that id arrives.
-// At the end the buffers are filtered to x >= min(x_t(final interval), m2) -- exactly a prefix of the ranking --
-// merged into one LDS array and handed to fast_tail.  A wave whose buffer overflows even after compaction makes
-// the stream take the old path: one more block sweep collects into global memory (sorted in LDS by fast_tail
-// when it fits, else by the device-wide sort and the list kernel).
-#ifndef NSG_WIDE_ONEPASS
-#define NSG_WIDE_ONEPASS 1
-#endif
-#ifndef NSG_WIDE_SPLIT
-#define NSG_WIDE_SPLIT 0  // 1: row stream and tail in two kernels (wide_onepass_kernel + wide_tail_kernel)
-#endif
-#ifndef NSG_TAIL_PRIO
-#define NSG_TAIL_PRIO 0  // s_setprio level of the one-pass kernel after its row stream (0: off)
-#endif
-#ifndef NSG_OP_RING
-#define NSG_OP_RING 4
-#endif
-constexpr int OP_CAPW = FAST_NL / FAST_WAVES;  // keys per wave buffer
 
 __device__ __forceinline__ float wave_sum_f32(float v) {
     v += __uint_as_float(xor_lane_u32<32>(__float_as_uint(v)));
@@ -1531,318 +1227,6 @@ __device__ __forceinline__ int wave_compact(uint64_t* wbuf, int cnt, float t) {
         nc += popc64(km);
     }
     return __builtin_amdgcn_readfirstlane(nc);
-}
-
-// ---- sort-free tail (round 3) -------------------------------------------------------------------------------
-// The CDF needs the kept keys' q_i in rank order only where a cumulative sum is SEARCHED (the overfill trim,
-// the selection, the received token's interval), and E no longer needs any order (canonical step 6).  So the
-// usual stream is finished without sorting its ~4,000 kept keys:
-//   1. every thread: its keys' exps and kept flags (not provably below the cutoff); wave sums of the limb mass,
-//      the kept count, the key range, an ambiguity flag -> one barrier -> E, k
-//   2. q_i and a 512-bucket histogram (monotone in the key: bucket order = rank order) of counts and q sums
-//      (LDS atomics) -> exclusive prefix per bucket (one bucket per thread, wave scans) -> the overfill bucket
-//   3. the kept keys scattered in bucket order (unordered inside a bucket)
-//   4. wave 0 ranks the few keys of the searched buckets among themselves (<= 64 each: lane-to-lane loop) and
-//      finishes the step: overfill trim, selection (encode) or the received token's rank (decode)
-// Anything else -- an ambiguous cutoff, k outside [2, topk], a bucket with more than 64 keys, a decode token that is
-// not kept or sits in the overfill bucket, statistics, the sampler -- returns false BEFORE s_keys is touched, and
-// the stream takes fast_tail (sort) as before.  Same integers: the kept set, E and every q_i are the canonical
-// step's; the searches give the first rank whose cumulative sum crosses the target, as the rank-order scans do.
-#ifndef NSG_NOSORT
-#define NSG_NOSORT 0  // sort-free tail (measured slower, A/B: DESIGN.md)
-#endif
-constexpr int NS_NB = FAST_THREADS;  // buckets (one per thread in the scan)
-
-__device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const uint64_t o = shfl_xor_u64(v, off);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const uint64_t o = shfl_xor_u64(v, off);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-__device__ __forceinline__ uint64_t readlane_u64(uint64_t v, int l) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);
-    return ((uint64_t)hi << 32) | lo;
-}
-
-struct KeysWave {  // slot r of a thread: entry r * 64 + lane of its wave's raw LDS buffer
-    const uint64_t* wbuf;
-    int mine;
-    __device__ __forceinline__ bool operator()(int r, uint64_t& key) const {
-        const int j = r * WAVE + (int)(threadIdx.x & (WAVE - 1));
-        key = j < mine ? op_raw_key(wbuf[j]) : 0ull;
-        return j < mine;
-    }
-};
-
-// own function (not inlined): its register demand stays out of the row-stream loop's allocation
-template <typename T, bool DECODE, typename KeyAt>
-__device__ __noinline__ bool nosort_tail(const StepParams& p, const WideStat* wsb, const int b, const KeyAt kin,
-                                         uint64_t* s_keys, uint64_t* s_aux) {
-    const WideStat w = *wsb;
-    const int tid = (int)threadIdx.x, lane = tid & (WAVE - 1), wv = tid / WAVE;
-    uint64_t* qb = s_aux;                       // [NS_NB] bucket q sums, then their exclusive prefix
-    uint32_t* cb = (uint32_t*)(s_aux + NS_NB);  // [NS_NB] bucket counts, then their exclusive prefix
-    uint64_t* pw = s_aux + NS_NB + NS_NB / 2;   // 256 words of per-wave partials
-    const ns_stream_state st = p.state[b];
-    const uint64_t R = st.hi - st.lo;
-    const double Rd = (double)R, thr = 1.0 / Rd;
-    const double inv_lo = 1.0 / (w.S_lo * (1.0 - 1.0e-15)), inv_hi = 1.0 / (w.S_hi * (1.0 + 1.0e-15));
-    const double m = (double)w.m;  // the row max = the largest collected key's value
-    // ---- 1. exps, kept flags, limb mass, key range (keys re-read from LDS in every phase and exps recomputed
-    // in step 2: register arrays of all slots would spill at the 80-VGPR occupancy budget)
-    auto e_of = [&](uint64_t k) __attribute__((always_inline)) -> double {
-        return exp_canon(((double)wkey_val(k) - m) * p.inv_temp);
-    };
-    uint32_t km = 0u;
-    Mass ms{0.0, 0.0, 0.0, 0.0};
-    uint64_t kmin = ~0ull, kmax = 0ull;
-    uint32_t nk = 0u;
-    bool amb = false;
-#pragma unroll
-    for (int r = 0; r < FAST_R; ++r) {
-        uint64_t k;
-        if (!kin(r, k)) continue;
-        kmax = k > kmax ? k : kmax;
-        const double e = e_of(k);
-        if (e * inv_lo < thr) continue;  // provably below the cutoff
-        amb |= !(e * inv_hi >= thr);     // neither provably below nor above: the exact sum decides
-        km |= 1u << r;
-        ++nk;
-        kmin = k < kmin ? k : kmin;
-        mass_add(ms, e);
-    }
-    mass_wave_sum(ms);
-    kmin = wave_min_u64(kmin);
-    kmax = wave_max_u64(kmax);
-    nk = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan_u32(nk), WAVE - 1);
-    const bool wamb = ballot(amb) != 0ull;
-    if (lane == 0) {
-        pw[8 * wv + 0] = __builtin_bit_cast(uint64_t, ms.a);
-        pw[8 * wv + 1] = __builtin_bit_cast(uint64_t, ms.b);
-        pw[8 * wv + 2] = __builtin_bit_cast(uint64_t, ms.c);
-        pw[8 * wv + 3] = __builtin_bit_cast(uint64_t, ms.d);
-        pw[8 * wv + 4] = kmin;
-        pw[8 * wv + 5] = kmax;
-        pw[8 * wv + 6] = (uint64_t)nk | ((uint64_t)(wamb ? 1u : 0u) << 32);
-    }
-    __syncthreads();
-    Mass tot{0.0, 0.0, 0.0, 0.0};
-    uint64_t kmin_a = ~0ull, kmax_a = 0ull;
-    int k0 = 0;
-    bool amb_a = false;
-#pragma unroll
-    for (int i = 0; i < FAST_WAVES; ++i) {
-        tot.a += __builtin_bit_cast(double, pw[8 * i + 0]);
-        tot.b += __builtin_bit_cast(double, pw[8 * i + 1]);
-        tot.c += __builtin_bit_cast(double, pw[8 * i + 2]);
-        tot.d += __builtin_bit_cast(double, pw[8 * i + 3]);
-        kmin_a = pw[8 * i + 4] < kmin_a ? pw[8 * i + 4] : kmin_a;
-        kmax_a = pw[8 * i + 5] > kmax_a ? pw[8 * i + 5] : kmax_a;
-        k0 += (int)(uint32_t)pw[8 * i + 6];
-        amb_a |= (pw[8 * i + 6] >> 32) != 0ull;
-    }
-    // decode: the received token must be a kept key (else fast_tail reports the divergence + ranked export)
-    uint64_t kt = 0ull;
-    if (DECODE) {
-        const int32_t tok = p.in_token[b];
-        if (tok >= 0 && tok < p.V && !is_banned(p, tok)) {
-            const char* rowc = (const char*)p.logits + (int64_t)b * p.ld * (int64_t)sizeof(T);
-            kt = wkey(Elem<T>::load1(rowc, tok), (uint32_t)tok);
-        }
-    }
-    if (amb_a || k0 < 2 || k0 > p.topk || (DECODE && !(kt >= kmin_a && kt <= kmax_a))) return false;
-    const double E = mass_value(tot);
-    NSG_STAMP(p, b, tid, 5);
-    // ---- 2. q and the bucket histogram (bucket 0 = the largest keys; monotone, so bucket order = rank order)
-    qb[tid] = 0ull;
-    cb[tid] = 0u;
-    __syncthreads();
-    const double bscale = (double)NS_NB / ((double)(kmax_a - kmin_a) + 1.0);
-    auto bucket_of = [&](uint64_t k) __attribute__((always_inline)) -> uint32_t {
-        return min((uint32_t)((double)(kmax_a - k) * bscale), (uint32_t)(NS_NB - 1));
-    };
-    uint32_t bs[FAST_R];
-#pragma unroll
-    for (int r = 0; r < FAST_R; ++r) {
-        bs[r] = 0u;
-        if ((km >> r) & 1u) {
-            uint64_t k;
-            kin(r, k);
-            const int64_t q = (int64_t)__builtin_rint((e_of(k) / E) * Rd);
-            const uint32_t bk = bucket_of(k);
-            bs[r] = (bk << 16) | atomicAdd(&cb[bk], 1u);
-            atomicAdd((unsigned long long*)&qb[bk], (unsigned long long)q);
-        }
-    }
-    __syncthreads();
-    // ---- 3. exclusive prefixes (thread t owns bucket t), the largest bucket, the overfill bucket
-    const uint32_t c = cb[tid];
-    const int64_t qv = (int64_t)qb[tid];
-    const uint32_t ci = wave_incl_scan_u32(c);
-    const int64_t qi = wave_incl_scan(qv, lane);
-    uint32_t occ = c;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) occ = max(occ, (uint32_t)__shfl_xor((int)occ, off));
-    if (lane == WAVE - 1) {
-        pw[64 + wv] = (uint64_t)qi;
-        pw[72 + wv] = (uint64_t)ci | ((uint64_t)occ << 32);
-    }
-    __syncthreads();
-    int64_t qbefore = 0, Q = 0;
-    uint32_t cbefore = 0u, maxocc = 0u;
-#pragma unroll
-    for (int i = 0; i < FAST_WAVES; ++i) {
-        const int64_t tq = (int64_t)pw[64 + i];
-        const uint32_t tc = (uint32_t)pw[72 + i];
-        if (i < wv) {
-            qbefore += tq;
-            cbefore += tc;
-        }
-        Q += tq;
-        maxocc = max(maxocc, (uint32_t)(pw[72 + i] >> 32));
-    }
-    if (maxocc > (uint32_t)WAVE) return false;  // a crowded bucket (skewed row): the sort path
-    NSG_STAMP(p, b, tid, 6);
-    const int64_t QP = qbefore + qi - qv;        // exclusive prefix of bucket tid
-    const uint32_t CP = cbefore + ci - c;
-    // overfill bucket: the first whose inclusive prefix exceeds R (NS_NB: none)
-    int ovf = (Q > (int64_t)R && QP + qv > (int64_t)R) ? tid : NS_NB;
-    ovf = wave_min_int(ovf);
-    // the decode token's bucket must lie before the overfill bucket (else the sort path checks it)
-    const int bt = DECODE ? (int)bucket_of(kt) : 0;
-    __syncthreads();  // every thread has read its bucket's count and sum
-    qb[tid] = (uint64_t)QP;
-    cb[tid] = CP;
-    if (lane == 0) pw[80 + wv] = (uint64_t)(uint32_t)ovf;
-    __syncthreads();
-    int b_ov = NS_NB;
-#pragma unroll
-    for (int i = 0; i < FAST_WAVES; ++i) b_ov = min(b_ov, (int)(uint32_t)pw[80 + i]);
-    if (DECODE && bt >= b_ov) return false;
-    // ---- 4. kept keys in bucket order: every thread holds its keys in registers before the first write
-    uint64_t kr[FAST_R];
-#pragma unroll
-    for (int r = 0; r < FAST_R; ++r) {
-        kr[r] = 0ull;
-        if ((km >> r) & 1u) kin(r, kr[r]);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < FAST_R; ++r)
-        if ((km >> r) & 1u) s_keys[cb[bs[r] >> 16] + (bs[r] & 0xFFFFu)] = kr[r];
-    __syncthreads();
-    if (wv != 0) return true;
-    NSG_STAMP(p, b, tid, 7);
-    // ---- 5. wave 0: resolve the searched buckets and finish the step
-    // member `lane` of bucket bk: its key, q, rank among the members, and cum = inclusive prefix at its rank
-    auto resolve = [&](int bk, uint64_t& key, int64_t& q, int& rank, int64_t& cum, int& occ_b)
-                       __attribute__((always_inline)) {
-        const int c0 = (int)cb[bk], c1 = bk + 1 < NS_NB ? (int)cb[bk + 1] : k0;
-        occ_b = c1 - c0;
-        const bool valid = lane < occ_b;
-        key = valid ? s_keys[c0 + lane] : 0ull;
-        q = valid ? (int64_t)__builtin_rint((e_of(key) / E) * Rd) : 0;
-        rank = 0;
-        int64_t ge = 0;
-        for (int o = 0; o < occ_b; ++o) {
-            const uint64_t ko = readlane_u64(key, o);
-            const int64_t qo = (int64_t)readlane_u64((uint64_t)q, o);
-            rank += ko > key ? 1 : 0;
-            ge += ko >= key ? qo : 0;
-        }
-        cum = (int64_t)qb[bk] + ge;
-    };
-    int kp = k0;
-    int64_t cumkp = Q;  // cum(kp - 1)
-    int kp_local = WAVE;
-    if (b_ov < NS_NB) {
-        uint64_t key;
-        int64_t q, cum;
-        int rank, occ_b;
-        resolve(b_ov, key, q, rank, cum, occ_b);
-        const bool over = lane < occ_b && cum > (int64_t)R;
-        kp_local = wave_min_int(over ? rank : WAVE);
-        kp = (int)cb[b_ov] + kp_local;
-        // cum(kp - 1): the member ranked kp_local - 1, or the prefix before the bucket
-        const bool prev = lane < occ_b && rank == kp_local - 1;
-        const uint64_t mp = ballot(prev);
-        cumkp = mp ? (int64_t)readlane_u64((uint64_t)cum, __builtin_ctzll(mp)) : (int64_t)qb[b_ov];
-    }
-    const int64_t shift = (int64_t)R - cumkp + (int64_t)st.lo;
-    int sel = -1;
-    int64_t cum_m1 = 0, cum_sel = 0;
-    uint64_t sel_key = 0ull;
-    if (!DECODE) {
-        const uint64_t idx = payload_window(p, b, st.bit_pos);
-        // first bucket (<= b_ov) whose inclusive cum + shift exceeds idx; 8 buckets per lane
-        int bs_l = NS_NB;
-#pragma unroll
-        for (int j = 0; j < NS_NB / WAVE; ++j) {
-            const int bk = lane * (NS_NB / WAVE) + j;
-            if (bk > b_ov) break;
-            const int64_t incl = bk == b_ov ? cumkp : (bk + 1 < NS_NB ? (int64_t)qb[bk + 1] : Q);
-            if ((uint64_t)(incl + shift) > idx) {
-                bs_l = bk;
-                break;
-            }
-        }
-        const int bsel = wave_min_int(bs_l);
-        if (bsel < NS_NB) {
-            uint64_t key;
-            int64_t q, cum;
-            int rank, occ_b;
-            resolve(bsel, key, q, rank, cum, occ_b);
-            const bool hit = lane < occ_b && (bsel != b_ov || rank < kp_local) && (uint64_t)(cum + shift) > idx;
-            const int rl = wave_min_int(hit ? rank : WAVE);
-            const uint64_t mh = ballot(hit && rank == rl);
-            if (mh) {
-                const int src = __builtin_ctzll(mh);
-                sel = (int)cb[bsel] + rl;
-                cum_sel = (int64_t)readlane_u64((uint64_t)cum, src);
-                cum_m1 = cum_sel - (int64_t)readlane_u64((uint64_t)q, src);
-                sel_key = readlane_u64(key, src);
-            }
-        }
-    } else {
-        uint64_t key;
-        int64_t q, cum;
-        int rank, occ_b;
-        resolve(bt, key, q, rank, cum, occ_b);
-        const uint64_t mh = ballot(lane < occ_b && key == kt);
-        if (mh) {
-            const int src = __builtin_ctzll(mh);
-            sel = (int)cb[bt] + __builtin_amdgcn_readlane(rank, src);
-            cum_sel = (int64_t)readlane_u64((uint64_t)cum, src);
-            cum_m1 = cum_sel - (int64_t)readlane_u64((uint64_t)q, src);
-            sel_key = kt;
-        }
-    }
-    if (lane != 0) return true;
-    if (sel < 0) {  // encode: no interval above the payload index (decode cannot get here: the token is kept)
-        p.state[b].flags = st.flags | (DECODE ? NS_ST_ERR_DIVERGE : NS_ST_ERR_RANGE) | NS_ST_DONE;
-        if (p.trace) {
-            ns_step_trace tr = {k0, kp, -1, -1, -1, 0, w.S_fast};
-            p.trace[b] = tr;
-        }
-        return true;
-    }
-    const RowStats rs{0.0, 0.0, 0.0};
-    wide_finish<DECODE>(p, b, st, k0, kp, sel, false, w.S_fast, sel > 0 ? cum_m1 : 0, cum_sel, shift, sel_key, m, rs,
-                        0.0, false);
-    NSG_STAMP(p, b, tid, 8);
-    NSG_STAMP_RT(p, b, tid, 10);
-    return true;
 }
 
 template <typename T, bool DECODE>
@@ -1975,9 +1359,6 @@ __global__ __launch_bounds__(FAST_THREADS, NSG_FAST_WAVES_PER_SIMD) void wide_on
     // appends: each lane's passing values go to consecutive slots (lane order, then value order inside the
     // lane): a per-lane count, one wave scan (DPP), predicated raw writes -- no per-value ballot/mbcnt
     auto append_tile = [&](int t, const float (&x)[W], uint32_t mb) __attribute__((always_inline)) {
-#if defined(NSG_OP_NOAPPEND)  // timing diagnostics: streaming and sums only
-        return;
-#endif
         uint32_t c = 0u;
 #pragma unroll
         for (int q = 0; q < W; ++q) c += (x[q] >= t_wave) ? 1u : 0u;
@@ -2086,7 +1467,6 @@ __global__ __launch_bounds__(FAST_THREADS, NSG_FAST_WAVES_PER_SIMD) void wide_on
                 sum_tile(x);
                 append_tile(t, x, mb);
             }
-#if !defined(NSG_OP_NOUPDATE)
             if ((j + 1) % UPD == 0 && t < se) {
                 // publish this wave's partial sum, read the others' (each a partial sum: whatever is read is a
                 // lower bound of the row sum), raise the threshold
@@ -2098,20 +1478,9 @@ __global__ __launch_bounds__(FAST_THREADS, NSG_FAST_WAVES_PER_SIMD) void wide_on
                 xt_run = uni_f32(fmaxf(xt_run, threshold(tot, p.sample ? wave_max(m1) : r)));
                 t_wave = xt_run;
             }
-#endif
         }
     }
-#if defined(NSG_OP_DIAG) && NSG_OP_DIAG == 1  // register-pressure / timing diagnostics: streaming only
-    if (lane == 0) s_part[wv] = (float)accS + accSf + (float)accT + m1 + (float)cnt;
-    if (tid == 0) count[b] = 0u;
-    return;
-#endif
     NSG_STAMP(p, b, tid, 2);
-#if NSG_TAIL_PRIO
-    // the rest of the step is a latency-bound chain of block reductions, barriers and fp64 work, sharing its SIMDs
-    // with the row streams of the other resident workgroups: give it issue priority
-    __builtin_amdgcn_s_setprio(NSG_TAIL_PRIO);
-#endif
 
     // ---- the row's statistics
     accS = wave_sum_butterfly(accS);
@@ -2253,7 +1622,6 @@ __global__ __launch_bounds__(FAST_THREADS, NSG_FAST_WAVES_PER_SIMD) void wide_on
     };
 
     int n = 0;
-    [[maybe_unused]] int n_before = 0;  // wave w's offset in the segment (split form only)
     bool from_lds = false;
     if (!any_ovf) {
         // ---- each wave filters its buffer to x >= xt_all in place; fast_tail reads the kept keys of its own
@@ -2263,10 +1631,7 @@ __global__ __launch_bounds__(FAST_THREADS, NSG_FAST_WAVES_PER_SIMD) void wide_on
         if (lane == 0) s_n[wv] = cnt;
         __syncthreads();
 #pragma unroll
-        for (int i = 0; i < FAST_WAVES; ++i) {
-            if (i < wv) n_before += s_n[i];
-            n += s_n[i];
-        }
+        for (int i = 0; i < FAST_WAVES; ++i) n += s_n[i];
         __syncthreads();
         from_lds = n >= 2 || n >= V - p.nbanned;
         // fewer than two ids clear the threshold (a peaked row: k >= 2 needs the second largest, which the
@@ -2296,14 +1661,6 @@ __global__ __launch_bounds__(FAST_THREADS, NSG_FAST_WAVES_PER_SIMD) void wide_on
     if (tid == 0) count[b] = (unsigned int)n;
     static_assert(FAST_R * WAVE == OP_CAPW, "one slot per buffer entry");
     NSG_STAMP(p, b, tid, 4);
-#if NSG_WIDE_SPLIT
-    // split form: the kept keys go to the stream's global segment (wave w's after those of waves < w) and
-    // wide_tail_kernel finishes the step, so this kernel carries no tail code (registers: the row stream only)
-    if (from_lds && n <= FAST_NL) {
-        for (int i = lane; i < cnt; i += WAVE) kout[n_before + i] = op_raw_key(wbuf[i]);
-    }
-    return;
-#endif
     const int mine = cnt;
     auto at = [&](int rr, uint64_t& key) __attribute__((always_inline)) -> bool {
         if (from_lds) {  // block-uniform
@@ -2315,1110 +1672,7 @@ __global__ __launch_bounds__(FAST_THREADS, NSG_FAST_WAVES_PER_SIMD) void wide_on
         key = i < n ? kout[i] : 0ull;
         return i < n;
     };
-#if NSG_NOSORT
-    if (from_lds && !(!DECODE && p.sample) && !w.exact && !(!DECODE && p.stats != nullptr)) {
-        if (nosort_tail<T, DECODE>(p, &ws[b], b, KeysWave{wbuf, mine}, s_keys, s_aux)) return;
-        __syncthreads();  // the partials area of s_aux is rewritten by fast_tail
-    }
-#endif
-    fast_tail<T, DECODE, true>(p, w, &ws[b], b, n, at, keys_out, cap, todo, s_keys, s_aux);
-}
-
-// ------------------------------------------------------------------------------------------ split-form tail
-// (round 3) The tail of the one-pass step as its own kernel: one 512-thread workgroup per stream reads the kept
-// keys wide_onepass_kernel wrote to the stream's segment and runs the sort-free tail, or the LDS sort tail
-// (fast_tail, exact row sum included) when the sort-free one does not apply.  Streams the one-pass kernel
-// handed to the device-wide sort (ws.pad) and inactive streams are skipped.  Without the row stream in the
-// same kernel the tail keeps its registers (no spills at the 80-VGPR budget of three workgroups per CU) and
-// never holds a row-stream slot.
-#ifndef NSG_TAIL_WAVES_PER_SIMD
-#define NSG_TAIL_WAVES_PER_SIMD 4  // 128 VGPRs: the tail's per-slot register arrays fit without spilling
-#endif
-template <typename T, bool DECODE>
-__global__ __launch_bounds__(FAST_THREADS, NSG_TAIL_WAVES_PER_SIMD) void wide_tail_kernel(
-    StepParams p, WideStat* ws, const uint64_t* keys_in, uint64_t* keys_out, const unsigned int* count, int cap,
-    unsigned int* todo) {
-    __shared__ uint64_t s_keys[FAST_NL];
-    __shared__ uint64_t s_aux[FAST_NB / 2];
-    const int b = blockIdx.x;
-    const WideStat w = ws[b];
-    if (!w.active || w.pad) return;
-    NSG_STAMP(p, b, (int)threadIdx.x, 11);
-    const int n = (int)count[b];
-    const KeysFlat kin{keys_in + (int64_t)b * cap, n};
-#if NSG_NOSORT
-    if (!(!DECODE && p.sample) && !w.exact && !(!DECODE && p.stats != nullptr)) {
-        if (nosort_tail<T, DECODE>(p, &ws[b], b, kin, s_keys, s_aux)) return;
-        __syncthreads();  // the partials area of s_aux is rewritten by fast_tail
-    }
-#endif
-    fast_tail<T, DECODE, true>(p, w, &ws[b], b, n, kin, keys_out, cap, todo, s_keys, s_aux);
-}
-
-// ------------------------------------------------------------------------------------------ wide step, round 4
-// The wide step as two kernels sized for occupancy rather than one workgroup per stream:
-//   wide_stream_kernel  one WAVE per stream (four streams per 256-thread workgroup, like the single-pass coder):
-//                       streams the row once with a 4-tile load ring, keeps the fast sum, the max and the
-//                       running collection threshold x_t = r + T ln(S_part / R) (any partial sum is a lower bound
-//                       of S, so x_t only rises), appends ids at or above it to an 8 KiB LDS buffer, compacts the
-//                       buffer to the current threshold when full and flushes it to the stream's global segment
-//                       (values and ids as two arrays) when it stays more than half full.  At the end: the proven
-//                       fast-sum interval (WideStat) and the final threshold xt; segment entries below xt are stale.
-//   wide_wtail_kernel   one 256-thread workgroup per stream, no key array: each pass streams the segment's values
-//                       again (L2 / Infinity Cache); pass A: exps, the cutoff (the kept set is x >= vk), the
-//                       order-free limb mass E; pass C: q_i and a 256-bucket histogram (bucket order = rank order)
-//                       of counts and q sums; one prefix per bucket; the members of the searched buckets (overfill,
-//                       selection, the decode token) gathered into LDS and ranked against each other.
-// Anything else -- an ambiguous cutoff or unusable bound (exact sum), k outside [2, topk], a crowded bucket, a
-// decode token that is not kept, an encode range error -- is handed, untouched, to the
-// device sort + wide_cdf_kernel (the list path) with its collected keys.  Statistics and the sampler keep the
-// one-pass kernel (host dispatch).
-constexpr int WS_WAVES = 4;                    // streams per stream-kernel workgroup
-constexpr int WS_CW = 1024;                    // LDS buffer entries per wave (8 KiB)
-#ifndef NSG_WS_NK
-#define NSG_WS_NK 4  // sample tiles (1,024 fp32 / 2,048 fp16 ids); 8 spill (the unpacked tiles stay live)
-#endif
-#ifndef NSG_WS_NR
-#define NSG_WS_NR 4
-#endif
-constexpr int WV_CW = 4096;                    // wave-per-stream step: LDS buffer entries (32 KiB)
-constexpr int WT_THREADS = 256;                // tail workgroup
-constexpr int WT_WAVES = WT_THREADS / WAVE;
-constexpr int WT_U = 4;                        // segment values in flight per tail thread
-constexpr int WT_LV = 8192;                    // segment values staged in LDS (32 KiB)
-constexpr int WT_NB = WT_THREADS;              // buckets (one per thread in the prefix)
-constexpr int WT_GM = 256;                     // members of one gathered bucket
-
-__device__ __forceinline__ float* seg_vals(uint64_t* keys, int b, int cap) { return (float*)(keys + (int64_t)b * cap); }
-// the id of segment entry i: 16-bit words when the vocabulary fits (V <= 65,536), else 32-bit
-__device__ __forceinline__ uint32_t seg_id(const uint32_t* gj, int i, bool id16) {
-    return id16 ? (uint32_t)((const uint16_t*)gj)[i] : gj[i];
-}
-__device__ __forceinline__ uint32_t* seg_ids(uint64_t* keys, int b, int cap) {
-    return (uint32_t*)(keys + (int64_t)b * cap) + cap;
-}
-
-// The sort-free tail of one stream by ONE wave, from the candidates in its LDS buffer (wbuf[0, n): raw entries,
-// all at or above the final threshold xt): the arithmetic of wide_wtail_kernel with wave-level reductions.  The
-// step is finished here (state, token / bits) and the stream marked inactive for the later kernels, or handed to
-// the hand-off list (keys to keys_out, pad) for an ambiguous cutoff, k outside [2, topk], a crowded bucket, a decode
-// token that is not kept, or an encode range error.
-template <typename T, bool DECODE>
-__device__ __forceinline__ void wave_tail(const StepParams& p, WideStat* wsb, WideStat w, int b,
-                                          const ns_stream_state& st, const uint64_t* wbuf, int n, uint64_t* keys_out,
-                                          unsigned int* count, int cap, unsigned int* todo) {
-    __shared__ uint32_t t_cnt[WT_NB];  // bucket counts, then their exclusive prefix
-    __shared__ uint64_t t_q[WT_NB];    // bucket q sums, then their exclusive prefix
-    __shared__ uint64_t t_mem[WT_GM];  // gathered members: keys
-    __shared__ int64_t t_memq[WT_GM];  //   and q
-    __shared__ uint32_t t_ctr;
-    const int lane = (int)(threadIdx.x & (WAVE - 1));
-    auto defer = [&](bool exact) __attribute__((always_inline)) {
-        uint64_t* ko = keys_out + (int64_t)b * cap;
-        for (int i = lane; i < n; i += WAVE) ko[i] = op_raw_key(wbuf[i]);
-        if (lane == 0) {
-            w.pad = 1u;
-            if (exact) w.exact = 1u;
-            w.nraw = 0u;
-            *wsb = w;
-            count[b] = (unsigned int)n;
-            todo[1 + atomicAdd(&todo[0], 1u)] = (unsigned int)b;
-        }
-    };
-    const uint64_t R = st.hi - st.lo;
-    const double Rd = (double)R, thr = 1.0 / Rd;
-    const double inv_lo = 1.0 / (w.S_lo * (1.0 - 1.0e-15)), inv_hi = 1.0 / (w.S_hi * (1.0 + 1.0e-15));
-    const double m = (double)w.m;
-    // ---- A: exps, cutoff (kept <=> x >= vk), order-free limb mass
-    Mass ms{0.0, 0.0, 0.0, 0.0};
-    uint32_t nk = 0u;
-    bool amb = false;
-    float vk = __builtin_inff();
-    for (int i = lane; i < n; i += WAVE) {
-        const float xv = op_raw_val(wbuf[i]);
-        const double e = exp_canon(((double)xv - m) * p.inv_temp);
-        if (e * inv_lo < thr) continue;
-        amb |= !(e * inv_hi >= thr);
-        ++nk;
-        vk = fminf(vk, xv);
-        mass_add(ms, e);
-    }
-    mass_wave_sum(ms);
-    const int k0 = __builtin_amdgcn_readlane((int)wave_incl_scan_u32(nk), WAVE - 1);
-    const bool amb_a = ballot(amb) != 0ull;
-    vk = -wave_max(-vk);
-    const double E = mass_value(ms);
-    float xtok = -__builtin_inff();
-    uint64_t kt = 0ull;
-    bool tok_ok = true;
-    if (DECODE) {
-        const int32_t tok = p.in_token[b];
-        tok_ok = tok >= 0 && tok < p.V && !is_banned(p, tok);
-        if (tok_ok) {
-            const char* rowc = (const char*)p.logits + (int64_t)b * p.ld * (int64_t)sizeof(T);
-            xtok = Elem<T>::load1(rowc, tok);
-            kt = wkey(xtok, (uint32_t)tok);
-            tok_ok = xtok >= vk;
-        }
-    }
-    if (amb_a || k0 < 2 || k0 > p.topk || k0 > p.K || !tok_ok || !(E > 0.0 && E <= 1.7976931348623157e308)) {
-        defer(amb_a);
-        return;
-    }
-    // ---- C: q and the bucket histogram over [vk, m]
-    const float fm = w.m;
-    const float bscale = fm > vk ? (float)WT_NB / (fm - vk) : 0.0f;
-    auto bucket_of = [&](float v) __attribute__((always_inline)) -> uint32_t {
-        return min((uint32_t)((fm - v) * bscale), (uint32_t)(WT_NB - 1));
-    };
-    auto q_of = [&](float v) __attribute__((always_inline)) -> int64_t {
-        return (int64_t)__builtin_rint((exp_canon(((double)v - m) * p.inv_temp) / E) * Rd);
-    };
-    for (int j = lane; j < WT_NB; j += WAVE) {
-        t_cnt[j] = 0u;
-        t_q[j] = 0ull;
-    }
-    lds_fence();
-    for (int i = lane; i < n; i += WAVE) {
-        const float xv = op_raw_val(wbuf[i]);
-        if (!(xv >= vk)) continue;
-        const uint32_t bk = bucket_of(xv);
-        atomicAdd(&t_cnt[bk], 1u);
-        atomicAdd((unsigned long long*)&t_q[bk], (unsigned long long)q_of(xv));
-    }
-    lds_fence();
-    // ---- prefixes: lane owns buckets 4 lane .. 4 lane + 3; the overfill bucket
-    constexpr int BPL = WT_NB / WAVE;
-    uint32_t cb[BPL];
-    int64_t qb[BPL];
-    uint32_t csum = 0u;
-    int64_t qsum = 0;
-#pragma unroll
-    for (int j = 0; j < BPL; ++j) {
-        cb[j] = t_cnt[BPL * lane + j];
-        qb[j] = (int64_t)t_q[BPL * lane + j];
-        csum += cb[j];
-        qsum += qb[j];
-    }
-    const uint32_t cincl = wave_incl_scan_u32(csum);
-    const int64_t qincl = wave_incl_scan(qsum, lane);
-    const int64_t Q = (int64_t)readlane_u64((uint64_t)qincl, WAVE - 1);
-    uint32_t cp = cincl - csum;
-    int64_t qp = qincl - qsum;
-    int ovf = WT_NB;
-#pragma unroll
-    for (int j = 0; j < BPL; ++j) {
-        t_cnt[BPL * lane + j] = cp;
-        t_q[BPL * lane + j] = (uint64_t)qp;
-        if (Q > (int64_t)R && qp + qb[j] > (int64_t)R && ovf == WT_NB) ovf = BPL * lane + j;
-        cp += cb[j];
-        qp += qb[j];
-    }
-    const int b_ov = wave_min_int(ovf);
-    lds_fence();
-    auto incl_of = [&](int bk) __attribute__((always_inline)) -> int64_t {
-        return bk + 1 < WT_NB ? (int64_t)t_q[bk + 1] : Q;
-    };
-    auto gather = [&](int bk) __attribute__((always_inline)) -> int {
-        if (lane == 0) t_ctr = 0u;
-        lds_fence();
-        for (int i = lane; i < n; i += WAVE) {
-            const uint64_t e = wbuf[i];
-            const float xv = op_raw_val(e);
-            if (!(xv >= vk) || (int)bucket_of(xv) != bk) continue;
-            const uint32_t at = atomicAdd(&t_ctr, 1u);
-            if (at < (uint32_t)WT_GM) {
-                t_mem[at] = op_raw_key(e);
-                t_memq[at] = q_of(xv);
-            }
-        }
-        lds_fence();
-        return (int)__builtin_amdgcn_readfirstlane((int)t_ctr);
-    };
-    struct Mem {
-        uint64_t key[WT_GM / WAVE];
-        int64_t q[WT_GM / WAVE], cum[WT_GM / WAVE];
-        int rank[WT_GM / WAVE];
-    };
-    auto resolve = [&](int bk, int nm, Mem& mm) __attribute__((always_inline)) {
-#pragma unroll
-        for (int j = 0; j < WT_GM / WAVE; ++j) {
-            const int i = lane + WAVE * j;
-            mm.key[j] = i < nm ? t_mem[i] : 0ull;
-            mm.q[j] = i < nm ? t_memq[i] : 0;
-            mm.rank[j] = 0;
-            mm.cum[j] = 0;
-        }
-        for (int o = 0; o < nm; ++o) {
-            const uint64_t ko = t_mem[o];
-            const int64_t qo = t_memq[o];
-#pragma unroll
-            for (int j = 0; j < WT_GM / WAVE; ++j) {
-                mm.rank[j] += ko > mm.key[j] ? 1 : 0;
-                mm.cum[j] += ko >= mm.key[j] ? qo : 0;
-            }
-        }
-        const int64_t base = (int64_t)t_q[bk];
-#pragma unroll
-        for (int j = 0; j < WT_GM / WAVE; ++j) mm.cum[j] += base;
-    };
-    auto crowded = [&]() __attribute__((always_inline)) {
-        if (lane == 0 && p.counters) atomicAdd(&p.counters[4 * (b & (NS_COUNTER_SHARDS - 1)) + 3], 1ull);
-        defer(false);
-    };
-    // ---- overfill: kp = first rank whose cum exceeds R
-    int kp = k0, kp_local = WT_GM + 1, nm_ov = -1;
-    int64_t cumkp = Q;
-    if (b_ov < WT_NB) {
-        nm_ov = gather(b_ov);
-        if (nm_ov > WT_GM) {
-            crowded();
-            return;
-        }
-        Mem mm;
-        resolve(b_ov, nm_ov, mm);
-        int kl = WT_GM + 1;
-#pragma unroll
-        for (int j = 0; j < WT_GM / WAVE; ++j)
-            if (lane + WAVE * j < nm_ov && mm.cum[j] > (int64_t)R) kl = min(kl, mm.rank[j]);
-        kl = wave_min_int(kl);
-        int64_t cprev = (int64_t)t_q[b_ov];
-#pragma unroll
-        for (int j = 0; j < WT_GM / WAVE; ++j) {
-            const uint64_t mp = ballot(lane + WAVE * j < nm_ov && mm.rank[j] == kl - 1);
-            if (mp) cprev = (int64_t)readlane_u64((uint64_t)mm.cum[j], __builtin_ctzll(mp));
-        }
-        kp_local = kl;
-        kp = (int)t_cnt[b_ov] + kl;
-        cumkp = cprev;
-    }
-    const int64_t shift = (int64_t)R - cumkp + (int64_t)st.lo;
-    // ---- the searched bucket
-    uint64_t idx = 0ull;
-    int bsel;
-    if (!DECODE) {
-        idx = payload_window(p, b, st.bit_pos);
-        int bl = WT_NB;
-#pragma unroll
-        for (int j = 0; j < BPL; ++j) {
-            const int bk = BPL * lane + j;
-            if (bk <= b_ov && bl == WT_NB) {
-                const int64_t inc = bk == b_ov ? cumkp : incl_of(bk);
-                if ((uint64_t)(inc + shift) > idx) bl = bk;
-            }
-        }
-        bsel = wave_min_int(bl);
-    } else {
-        bsel = (int)bucket_of(xtok);
-    }
-    if (bsel >= WT_NB || bsel > b_ov) {
-        defer(false);
-        return;
-    }
-    const int nm = bsel == b_ov ? nm_ov : gather(bsel);
-    if (nm > WT_GM) {
-        crowded();
-        return;
-    }
-    Mem mm;
-    resolve(bsel, nm, mm);
-    int rl = WT_GM + 1;
-#pragma unroll
-    for (int j = 0; j < WT_GM / WAVE; ++j) {
-        const bool valid = lane + WAVE * j < nm && (bsel != b_ov || mm.rank[j] < kp_local);
-        const bool hit = DECODE ? (valid && mm.key[j] == kt) : (valid && (uint64_t)(mm.cum[j] + shift) > idx);
-        if (hit) rl = min(rl, mm.rank[j]);
-    }
-    rl = wave_min_int(rl);
-    if (rl > WT_GM) {
-        defer(false);
-        return;
-    }
-    int64_t cum_sel = 0, q_sel = 0;
-    uint64_t key_sel = 0ull;
-#pragma unroll
-    for (int j = 0; j < WT_GM / WAVE; ++j) {
-        const uint64_t mh = ballot(lane + WAVE * j < nm && mm.rank[j] == rl);
-        if (mh) {
-            const int src = __builtin_ctzll(mh);
-            cum_sel = (int64_t)readlane_u64((uint64_t)mm.cum[j], src);
-            q_sel = (int64_t)readlane_u64((uint64_t)mm.q[j], src);
-            key_sel = readlane_u64(mm.key[j], src);
-        }
-    }
-    if (lane == 0) {
-        const int sel = (int)t_cnt[bsel] + rl;
-        const RowStats rs{0.0, 0.0, 0.0};
-        wide_finish<DECODE>(p, b, st, k0, kp, sel, false, w.S_fast, sel > 0 ? cum_sel - q_sel : 0, cum_sel, shift,
-                            key_sel, m, rs, 0.0, false);
-        w.active = 0u;  // finished: the tail kernel, the hand-off list and the device sort skip it
-        w.nraw = 0u;
-        *wsb = w;
-        count[b] = 0u;
-    }
-    NSG_STAMP(p, b, lane, 8);
-    NSG_STAMP_RT(p, b, lane, 10);
-}
-
-// NWV waves (streams) per workgroup, CW buffer entries per wave, NR tiles in flight per wave.  INTAIL (the
-// wave-per-stream step, wide_wave_kernel below): a wave whose candidates stayed in its buffer finishes the step
-// itself (wave_tail); the others leave their segment to wide_wtail_kernel.
-template <typename T, bool DECODE, int NWV, int CW, int NR, bool INTAIL>
-__device__ __forceinline__ void wide_stream_body(const StepParams& p, WideStat* ws, uint64_t* keys_in,
-                                                 uint64_t* keys_out, unsigned int* count, int cap,
-                                                 unsigned int* todo, uint64_t (*s_buf)[CW]) {
-    constexpr int W = Elem<T>::W;
-    constexpr int TS = WAVE * W;
-    constexpr int WS_NK = NSG_WS_NK;  // sample tiles (in registers during the prologue, skipped by the stream)
-    constexpr int WS_CW = CW;
-    const int lane = (int)(threadIdx.x & (WAVE - 1));
-    const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x / WAVE);
-    const int b = __builtin_amdgcn_readfirstlane((int)blockIdx.x * NWV + wv);
-    if (b >= p.B) return;
-    const ns_stream_state st = p.state[b];
-    bool active = !(st.flags & NS_ST_DONE);
-    if (!DECODE && active && st.bit_pos >= p.nbits[b]) {
-        if (lane == 0 && !(p.flags & NS_STEP_FINISH_SENT)) p.state[b].flags = st.flags | NS_ST_DONE;
-        active = false;
-    }
-    if (DECODE && p.active && !p.active[b]) active = false;
-    if (!active) {
-        if (lane == 0) {
-            ws[b].active = 0;
-            count[b] = 0;
-        }
-        return;
-    }
-    NSG_STAMP_RT(p, b, lane, 9);
-    NSG_STAMP(p, b, lane, 0);
-    const int V = p.V;
-    const char* rowc = (const char*)p.logits + (int64_t)b * p.ld * (int64_t)sizeof(T);
-    const RowReader rd(rowc, (uint32_t)(p.ld * (int64_t)sizeof(T)));
-    const int ntiles = (V + TS - 1) / TS;
-    const double temp = 1.0 / p.inv_temp;
-    const float tempf = (float)temp;
-    const double Rd = (double)(st.hi - st.lo);
-    const float lnthr = (float)(-log(Rd));
-    uint64_t* wbuf = s_buf[wv];
-    float* gv = seg_vals(keys_in, b, cap);
-    uint32_t* gj = seg_ids(keys_in, b, cap);
-    uint16_t* gj16 = (uint16_t*)gj;
-    const bool id16 = V <= 65536;  // ids as 16-bit words: 6 bytes per segment entry
-
-    // masked ids (past the row, banned): -1e30 and bit q of mb (never collected), bans walked in tile order
-    int bi = 0, next_ban = 0x7FFFFFFF;
-    auto ban_reset = [&]() __attribute__((always_inline)) {
-        bi = 0;
-        next_ban = p.nbanned > 0 ? p.banned[0] : 0x7FFFFFFF;
-    };
-    auto load_x = [&](int t, const uint4& raw, float (&x)[W], uint32_t& mb) __attribute__((always_inline)) {
-        Elem<T>::unpack(raw, x);
-        mb = 0u;
-        const int j0 = t * TS + lane * W;
-        if ((t + 1) * TS > V) {
-#pragma unroll
-            for (int q = 0; q < W; ++q)
-                if (j0 + q >= V) {
-                    x[q] = -1.0e30f;
-                    mb |= 1u << q;
-                }
-        }
-        while (next_ban < t * TS) {  // bans of skipped tiles
-            ++bi;
-            next_ban = bi < p.nbanned ? p.banned[bi] : 0x7FFFFFFF;
-        }
-        while (next_ban < (t + 1) * TS) {
-            const int d = next_ban - j0;
-            if (d >= 0 && d < W) {
-#pragma unroll
-                for (int q = 0; q < W; ++q)
-                    if (q == d) {
-                        x[q] = -1.0e30f;
-                        mb |= 1u << q;
-                    }
-            }
-            ++bi;
-            next_ban = bi < p.nbanned ? p.banned[bi] : 0x7FFFFFFF;
-        }
-    };
-    float r = 0.0f, nrc = 0.0f;
-    float m1 = -__builtin_inff();
-    double accS = 0.0, accT = 0.0;
-    float accSf = 0.0f;
-    auto sum_tile = [&](const float (&x)[W]) __attribute__((always_inline)) {
-        typedef float f2 __attribute__((ext_vector_type(2)));
-        const f2 c2 = {p.c32, p.c32}, n2 = {nrc, nrc};
-        f2 a2 = {0.0f, 0.0f}, b2 = {0.0f, 0.0f};
-#pragma unroll
-        for (int q = 0; q < W; q += 2) {
-            const f2 x2 = {x[q], x[q + 1]};
-            const f2 t = __builtin_elementwise_fma(x2, c2, n2);
-            const f2 e2 = {__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
-            a2 += e2;
-            b2 = __builtin_elementwise_fma(e2, t, b2);
-            m1 = __builtin_fmaxf(__builtin_fmaxf(m1, x[q]), x[q + 1]);
-        }
-        const float a = a2.x + a2.y;
-        accS += (double)a;
-        accT += (double)(b2.x + b2.y);
-        accSf += a;
-    };
-    int cnt = 0;       // entries in the LDS buffer (wave-uniform)
-    uint32_t gcnt = 0;  // entries flushed to the segment
-    float t_wave = -__builtin_inff();
-    auto flush = [&]() __attribute__((always_inline)) {
-        for (int i = lane; i < cnt; i += WAVE) {
-            const uint64_t e = wbuf[i];
-            gv[gcnt + i] = op_raw_val(e);
-            if (id16)
-                gj16[gcnt + i] = (uint16_t)e;
-            else
-                gj[gcnt + i] = (uint32_t)e;
-        }
-        gcnt += (uint32_t)cnt;
-        cnt = 0;
-    };
-    auto append_tile = [&](int t, const float (&x)[W], uint32_t mb) __attribute__((always_inline)) {
-#ifdef NSG_WS_NOAPPEND
-        return;
-#endif
-        uint32_t c = 0u;
-#pragma unroll
-        for (int q = 0; q < W; ++q) c += (x[q] >= t_wave && !((mb >> q) & 1u)) ? 1u : 0u;
-        const uint32_t incl = wave_incl_scan_u32(c);
-        const int tot = __builtin_amdgcn_readlane((int)incl, WAVE - 1);
-        if (tot == 0) return;
-        if (cnt + tot > WS_CW) {
-            cnt = wave_compact(wbuf, cnt, t_wave);
-            if (cnt + tot > WS_CW || 2 * cnt > WS_CW) flush();
-        }
-        uint32_t pos = (uint32_t)cnt + incl - c;
-        const uint32_t j0 = (uint32_t)(t * TS + lane * W);
-#pragma unroll
-        for (int q = 0; q < W; ++q)
-            if (x[q] >= t_wave && !((mb >> q) & 1u)) wbuf[pos++] = op_raw(x[q], j0 + q);
-        cnt += tot;
-    };
-    auto threshold = [&](float s_part) __attribute__((always_inline)) -> float {
-        if (!(s_part > 0.0f && s_part < 3.0e38f)) return -__builtin_inff();
-        const float L = __builtin_amdgcn_logf(s_part * 0.9990234375f) * 0.6931471805599453f + lnthr;
-        const float t = r + tempf * L;
-        return t - 1.0e-4f * (1.0f + fabsf(r) + fabsf(tempf * L));
-    };
-
-    // ---- sample: WS_NK whole tiles spread over the row (tile s*space + space-1) give r and the first threshold;
-    // the ring's first tiles are in flight behind them.  Small rows (fewer than 2*WS_NK tiles): r = max of tile 0.
-    const bool spec = ntiles >= 2 * WS_NK;
-    const int space = spec ? ntiles / WS_NK : 1;
-    const int nstream = spec ? ntiles - WS_NK : ntiles;
-    int lt = 0, lc = spec ? space - 1 : 0x7FFFFFFF, sleft = spec ? WS_NK : 0;
-    auto next_tile = [&]() __attribute__((always_inline)) -> int {
-        const int t = lt++;
-        if (--lc == 0) {
-            ++lt;
-            lc = --sleft > 0 ? space - 1 : 0x7FFFFFFF;
-        }
-        return t;
-    };
-    uint4 smp[WS_NK];
-    if (spec) {
-#pragma unroll
-        for (int s = 0; s < WS_NK; ++s) smp[s] = rd.vec((s * space + space - 1) * WAVE + lane);
-    }
-    uint4 ring[NR];
-    int rt[NR];
-#pragma unroll
-    for (int d = 0; d < NR; ++d) {
-        rt[d] = next_tile();
-        ring[d] = rd.vec(rt[d] * WAVE + lane);
-    }
-    float xt_run = -__builtin_inff();
-    if (spec) {
-        float smax = -__builtin_inff();
-        ban_reset();
-#pragma unroll
-        for (int s = 0; s < WS_NK; ++s) {
-            float x[W];
-            uint32_t mb;
-            load_x(s * space + space - 1, smp[s], x, mb);
-#pragma unroll
-            for (int q = 0; q < W; ++q) smax = fmaxf(smax, x[q]);
-        }
-        r = wave_max(smax);
-        if (!(r > -1.0e29f)) r = 0.0f;
-        nrc = -(r * p.c32);
-        ban_reset();
-#pragma unroll
-        for (int s = 0; s < WS_NK; ++s) {
-            float x[W];
-            uint32_t mb;
-            load_x(s * space + space - 1, smp[s], x, mb);
-            sum_tile(x);
-        }
-        xt_run = threshold(wave_sum_f32(accSf));
-        t_wave = xt_run;
-        ban_reset();
-#pragma unroll
-        for (int s = 0; s < WS_NK; ++s) {
-            float x[W];
-            uint32_t mb;
-            load_x(s * space + space - 1, smp[s], x, mb);
-            append_tile(s * space + space - 1, x, mb);
-        }
-    } else {
-        float x[W];
-        uint32_t mb;
-        ban_reset();
-        load_x(0, ring[0], x, mb);
-        float mx = x[0];
-#pragma unroll
-        for (int q = 1; q < W; ++q) mx = fmaxf(mx, x[q]);
-        r = wave_max(mx);
-        if (!(r > -1.0e29f)) r = 0.0f;
-        nrc = -(r * p.c32);
-    }
-    NSG_STAMP(p, b, lane, 1);
-
-    // ---- the stream: ring groups of NR tiles; the threshold rises once per group
-    ban_reset();
-    int pos = 0;
-    for (; pos + NR <= nstream; pos += NR) {
-        // one tile at a time (its slot refilled as soon as it is unpacked): a single tile's values are live
-#pragma unroll
-        for (int d = 0; d < NR; ++d) {
-            const int jt = rt[d];
-            float x[W];
-            uint32_t mb;
-            load_x(jt, ring[d], x, mb);
-            rt[d] = next_tile();
-            ring[d] = rd.vec(rt[d] * WAVE + lane);
-            sum_tile(x);
-            append_tile(jt, x, mb);
-        }
-        xt_run = fmaxf(xt_run, threshold(wave_sum_f32(accSf)));
-        t_wave = xt_run;
-    }
-#pragma unroll
-    for (int d = 0; d < NR; ++d) {
-        if (pos + d < nstream) {
-            float x[W];
-            uint32_t mb;
-            load_x(rt[d], ring[d], x, mb);
-            sum_tile(x);
-            append_tile(rt[d], x, mb);
-        }
-    }
-    NSG_STAMP(p, b, lane, 2);
-
-    // ---- the proven interval, the final threshold, the buffer filtered to it and flushed
-    accS = wave_sum_butterfly(accS);
-    accT = wave_sum_butterfly(accT);
-    float bm1 = wave_max(m1);
-    if (!(bm1 > -1.0e29f)) bm1 = -__builtin_inff();
-    WideStat w;
-    double Sf = 0.0, S_lo = 0.0, S_hi = 0.0;
-    const bool ok = fast_sum_interval_dd(accS, accT, r, (double)(bm1 + 0.0f), p.c32, p.inv_temp, W, Sf, S_lo, S_hi);
-    w.m = bm1;
-    w.m2 = -__builtin_inff();
-    w.r = r;
-    w.active = 1;
-    w.S_lo = S_lo;
-    w.S_hi = S_hi;
-    w.S_fast = Sf;
-    w.exact = (ok && !(p.flags & NS_STEP_FORCE_EXACT_SUM)) ? 0u : 1u;
-    w.pad = 0;
-    w.S_r = accS;
-    w.B_r = 0.0;
-    w.U_r = 0.0;
-    float xt = -__builtin_inff();
-    if (ok) {
-        const double L = log(S_lo / Rd);
-        const double t = (double)w.m + temp * L;
-        xt = (float)(t - 1.0e-4 * (1.0 + fabs((double)w.m) + fabs(temp * L)));
-    }
-    xt = fmaxf(xt, xt_run);
-    t_wave = xt;
-    cnt = wave_compact(wbuf, cnt, t_wave);
-    w.xt = xt;
-    if constexpr (INTAIL) {
-        // every candidate is still in the buffer: this wave finishes the step (else the segment goes to the tail
-        // kernel, which also takes the exact row sum and the sweep for a peaked row)
-        if (gcnt == 0 && !w.exact && cnt >= 2) {
-            NSG_STAMP(p, b, lane, 3);
-            wave_tail<T, DECODE>(p, &ws[b], w, b, st, wbuf, cnt, keys_out, count, cap, todo);
-            return;
-        }
-    }
-    flush();
-    w.nraw = gcnt;
-    if (lane == 0) {
-        ws[b] = w;
-        count[b] = gcnt;
-    }
-    NSG_STAMP(p, b, lane, 3);
-}
-
-template <typename T, bool DECODE>
-__global__ __launch_bounds__(WS_WAVES* WAVE, 4) void wide_stream_kernel(StepParams p, WideStat* ws, uint64_t* keys_in,
-                                                                        unsigned int* count, int cap,
-                                                                        unsigned int* todo, unsigned int* todo2) {
-    __shared__ uint64_t s_buf[WS_WAVES][WS_CW];
-    if (blockIdx.x == 0 && threadIdx.x == 0) {  // the step's two work lists start empty (no memset launches)
-        todo[0] = 0u;
-        todo2[0] = 0u;
-    }
-    wide_stream_body<T, DECODE, WS_WAVES, WS_CW, NSG_WS_NR, false>(p, ws, keys_in, nullptr, count, cap, todo, s_buf);
-}
-
-// the wave-per-stream step: one 64-thread workgroup per stream, a WV_CW-entry LDS buffer (its ~4,000 kept ids
-// stay on chip), a WV_NR-tile load ring (one wave per SIMD: the ring is what keeps bytes in flight), the tail in
-// the same wave
-#ifndef NSG_WV_NR
-#define NSG_WV_NR 12
-#endif
-template <typename T, bool DECODE>
-__global__ __launch_bounds__(WAVE, 1) void wide_wave_kernel(StepParams p, WideStat* ws, uint64_t* keys_in,
-                                                            uint64_t* keys_out, unsigned int* count, int cap,
-                                                            unsigned int* todo, unsigned int* todo2) {
-    __shared__ uint64_t s_buf[1][WV_CW];
-    if (blockIdx.x == 0 && threadIdx.x == 0) todo2[0] = 0u;  // the hand-off kernel's list (todo: memset before)
-    wide_stream_body<T, DECODE, 1, WV_CW, NSG_WV_NR, true>(p, ws, keys_in, keys_out, count, cap, todo, s_buf);
-}
-
-// the list path for one stream of the tail kernel: its collected keys (x >= xt) go to keys_out (unsorted) for the
-// device sort; exact: the list kernel computes the exact row sum.  Fewer than two keys (a peaked row whose second
-// largest value is below the running threshold): the row is swept again for x >= min(xt, second largest).
-template <typename T>
-__device__ void wtail_defer(const StepParams& p, WideStat* wsb, int b, const float* gv, const uint32_t* gj, int n,
-                            float xt, uint64_t* keys_out, unsigned int* count, int cap, unsigned int* todo, bool exact,
-                            uint32_t* s_ctr, float* s_top) {
-    const int tid = (int)threadIdx.x, lane = tid & (WAVE - 1), wv = tid / WAVE;
-    uint64_t* ko = keys_out + (int64_t)b * cap;
-    __syncthreads();
-    if (tid == 0) *s_ctr = 0u;
-    __syncthreads();
-    for (int i = tid; i < n; i += WT_THREADS) {
-        const float v = gv[i];
-        if (v >= xt) ko[atomicAdd(s_ctr, 1u)] = wkey(v, seg_id(gj, i, p.V <= 65536));
-    }
-    __syncthreads();
-    uint32_t got = *s_ctr;
-    if (got < 2u && (int)got < p.V - p.nbanned) {
-        // the row's two largest valid values, then every valid id at or above the second one (block sweeps)
-        constexpr int W = Elem<T>::W;
-        const char* rowc = (const char*)p.logits + (int64_t)b * p.ld * (int64_t)sizeof(T);
-        const RowReader rd(rowc, (uint32_t)(p.ld * (int64_t)sizeof(T)));
-        const int nvec = (p.V + W - 1) / W;
-        float l1 = -__builtin_inff(), l2 = -__builtin_inff();
-        for (int v = tid; v < nvec; v += WT_THREADS) {
-            float x[W];
-            Elem<T>::unpack(rd.vec(v), x);
-#pragma unroll
-            for (int q = 0; q < W; ++q) {
-                const int j = v * W + q;
-                const float y = (j < p.V && !is_banned(p, j)) ? x[q] : -__builtin_inff();
-                l2 = fmaxf(l2, fminf(l1, y));
-                l1 = fmaxf(l1, y);
-            }
-        }
-        wave_top2(l1, l2);
-        if (lane == 0) {
-            s_top[2 * wv] = l1;
-            s_top[2 * wv + 1] = l2;
-        }
-        __syncthreads();
-        float b1 = -__builtin_inff(), b2 = -__builtin_inff();
-#pragma unroll
-        for (int i = 0; i < WT_WAVES; ++i) {
-            b2 = fmaxf(fminf(b1, s_top[2 * i]), fmaxf(b2, s_top[2 * i + 1]));
-            b1 = fmaxf(b1, s_top[2 * i]);
-        }
-        const float thr = fminf(xt, b2);
-        if (tid == 0) *s_ctr = 0u;
-        __syncthreads();
-        for (int v = tid; v < nvec; v += WT_THREADS) {
-            float x[W];
-            Elem<T>::unpack(rd.vec(v), x);
-#pragma unroll
-            for (int q = 0; q < W; ++q) {
-                const int j = v * W + q;
-                if (j < p.V && !is_banned(p, j) && x[q] >= thr) {
-                    const uint32_t at = atomicAdd(s_ctr, 1u);
-                    if (at < (uint32_t)cap) ko[at] = wkey(x[q], (uint32_t)j);
-                }
-            }
-        }
-        __syncthreads();
-        got = min(*s_ctr, (uint32_t)cap);
-        if (tid == 0 && p.counters) atomicAdd(&p.counters[4 * (b & (NS_COUNTER_SHARDS - 1)) + 1], 1ull);
-    }
-    if (tid == 0) {
-        count[b] = got;
-        wsb->pad = 1u;
-        if (exact) wsb->exact = 1u;
-        todo[1 + atomicAdd(&todo[0], 1u)] = (unsigned int)b;
-    }
-}
-
-#ifndef NSG_WT_WAVES_PER_SIMD
-#define NSG_WT_WAVES_PER_SIMD 4  // 40 KiB of LDS per workgroup: four per CU
-#endif
-template <typename T, bool DECODE>
-__global__ __launch_bounds__(WT_THREADS, NSG_WT_WAVES_PER_SIMD) void wide_wtail_kernel(
-    StepParams p, WideStat* ws, uint64_t* keys_in, uint64_t* keys_out, unsigned int* count, int cap,
-    unsigned int* todo) {
-    __shared__ uint32_t s_cnt[WT_NB];   // bucket counts, then their exclusive prefix
-    __shared__ uint64_t s_q[WT_NB];     // bucket q sums, then their exclusive prefix
-    __shared__ uint64_t s_mem[WT_GM];   // members of the searched bucket: keys
-    __shared__ int64_t s_memq[WT_GM];   //   and q
-    __shared__ double s_d[4 * WT_WAVES];
-    __shared__ uint64_t s_w[8 * WT_WAVES];
-    __shared__ uint32_t s_ctr[4];
-    __shared__ float s_top[2 * WT_WAVES];
-    __shared__ int64_t s_res[8];
-    __shared__ float s_vals[WT_LV];
-    const int b = blockIdx.x;
-    WideStat* wsb = &ws[b];
-    const WideStat w = *wsb;
-    if (!w.active || w.pad) return;  // finished by the wave-per-stream step, or already on the hand-off list
-    const int tid = (int)threadIdx.x, lane = tid & (WAVE - 1), wv = tid / WAVE;
-    NSG_STAMP(p, b, tid, 11);
-    float* gv = seg_vals(keys_in, b, cap);
-    uint32_t* gj = seg_ids(keys_in, b, cap);
-    const float xt = w.xt;
-    int n = (int)w.nraw;
-    const ns_stream_state st = p.state[b];
-    if (w.exact) {
-        wtail_defer<T>(p, wsb, b, gv, gj, n, xt, keys_out, count, cap, todo, true, s_ctr, s_top);
-        return;
-    }
-    // the segment's values are read once into LDS (up to WT_LV of them; a longer segment -- a flat row -- is
-    // streamed from global memory by every pass); stale entries (x < xt) are skipped by every pass
-    const float* src = gv;
-    if (n <= WT_LV) {
-        for (int i = tid; i < n; i += WT_THREADS) s_vals[i] = gv[i];
-        __syncthreads();
-        src = s_vals;
-    }
-    auto for_each = [&](auto&& fn) __attribute__((always_inline)) {
-        for (int i0 = tid; i0 < n; i0 += WT_U * WT_THREADS) {
-            float xv[WT_U];
-#pragma unroll
-            for (int u = 0; u < WT_U; ++u) {
-                const int i = i0 + u * WT_THREADS;
-                xv[u] = i < n ? src[i] : -__builtin_inff();
-            }
-#pragma unroll
-            for (int u = 0; u < WT_U; ++u)
-                if (xv[u] >= xt) fn(xv[u], i0 + u * WT_THREADS);
-        }
-    };
-    s_cnt[tid] = 0u;
-    s_q[tid] = 0ull;
-    const uint64_t R = st.hi - st.lo;
-    const double Rd = (double)R, thr = 1.0 / Rd;
-    const double inv_lo = 1.0 / (w.S_lo * (1.0 - 1.0e-15)), inv_hi = 1.0 / (w.S_hi * (1.0 + 1.0e-15));
-    const double m = (double)w.m;
-    // ---- A: exps, cutoff, limb mass (the kept set is x >= vk: e is monotone in x)
-    Mass ms{0.0, 0.0, 0.0, 0.0};
-    uint32_t nk = 0u;
-    bool amb = false;
-    float vk = __builtin_inff();
-    for_each([&](float xv, int) __attribute__((always_inline)) {
-        const double e = exp_canon(((double)xv - m) * p.inv_temp);
-        if (e * inv_lo < thr) return;
-        amb |= !(e * inv_hi >= thr);
-        ++nk;
-        vk = fminf(vk, xv);
-        mass_add(ms, e);
-    });
-    mass_wave_sum(ms);
-    {
-        const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan_u32(nk), WAVE - 1);
-        const float wvk = -wave_max(-vk);
-        const bool wamb = ballot(amb) != 0ull;
-        if (lane == 0) {
-            s_d[4 * wv + 0] = ms.a;
-            s_d[4 * wv + 1] = ms.b;
-            s_d[4 * wv + 2] = ms.c;
-            s_d[4 * wv + 3] = ms.d;
-            s_w[wv] = (uint64_t)tot | ((uint64_t)(wamb ? 1u : 0u) << 32);
-            s_top[wv] = wvk;
-        }
-    }
-    __syncthreads();
-    Mass tot{0.0, 0.0, 0.0, 0.0};
-    int k0 = 0;
-    bool amb_a = false;
-    vk = __builtin_inff();
-#pragma unroll
-    for (int i = 0; i < WT_WAVES; ++i) {
-        tot.a += s_d[4 * i + 0];
-        tot.b += s_d[4 * i + 1];
-        tot.c += s_d[4 * i + 2];
-        tot.d += s_d[4 * i + 3];
-        k0 += (int)(uint32_t)s_w[i];
-        amb_a |= (s_w[i] >> 32) != 0ull;
-        vk = fminf(vk, s_top[i]);
-    }
-    const double E = mass_value(tot);
-    // decode: the received token must be kept (x >= vk), else the list path reports the divergence
-    float xtok = -__builtin_inff();
-    uint64_t kt = 0ull;
-    bool tok_ok = true;
-    if (DECODE) {
-        const int32_t tok = p.in_token[b];
-        tok_ok = tok >= 0 && tok < p.V && !is_banned(p, tok);
-        if (tok_ok) {
-            const char* rowc = (const char*)p.logits + (int64_t)b * p.ld * (int64_t)sizeof(T);
-            xtok = Elem<T>::load1(rowc, tok);
-            kt = wkey(xtok, (uint32_t)tok);
-            tok_ok = xtok >= vk;
-        }
-    }
-    if (amb_a || k0 < 2 || k0 > p.topk || k0 > p.K || !tok_ok || !(E > 0.0 && E <= 1.7976931348623157e308)) {
-        wtail_defer<T>(p, wsb, b, gv, gj, n, xt, keys_out, count, cap, todo, amb_a, s_ctr, s_top);
-        return;
-    }
-    NSG_STAMP(p, b, tid, 5);
-    // ---- C: q_i and the bucket histogram over [vk, m] (linear in x: monotone, ties share a bucket)
-    const float fm = w.m;
-    const float bscale = fm > vk ? (float)WT_NB / (fm - vk) : 0.0f;
-    auto bucket_of = [&](float v) __attribute__((always_inline)) -> uint32_t {
-        return min((uint32_t)((fm - v) * bscale), (uint32_t)(WT_NB - 1));
-    };
-    for_each([&](float xv, int) __attribute__((always_inline)) {
-        if (!(xv >= vk)) return;  // kept <=> x >= vk
-        const double e = exp_canon(((double)xv - m) * p.inv_temp);
-        const uint64_t q = (uint64_t)(int64_t)__builtin_rint((e / E) * Rd);
-        const uint32_t bk = bucket_of(xv);
-        atomicAdd(&s_cnt[bk], 1u);
-        atomicAdd((unsigned long long*)&s_q[bk], (unsigned long long)q);
-    });
-    __syncthreads();
-    // ---- prefixes (thread t owns bucket t), the overfill bucket
-    const uint32_t c = s_cnt[tid];
-    const int64_t qv = (int64_t)s_q[tid];
-    const uint32_t ci = wave_incl_scan_u32(c);
-    const int64_t qi = wave_incl_scan(qv, lane);
-    if (lane == WAVE - 1) {
-        s_w[8 + wv] = (uint64_t)qi;
-        s_w[16 + wv] = (uint64_t)ci;
-    }
-    __syncthreads();
-    int64_t qbefore = 0, Q = 0;
-    uint32_t cbefore = 0u;
-#pragma unroll
-    for (int i = 0; i < WT_WAVES; ++i) {
-        const int64_t tq = (int64_t)s_w[8 + i];
-        if (i < wv) {
-            qbefore += tq;
-            cbefore += (uint32_t)s_w[16 + i];
-        }
-        Q += tq;
-    }
-    const int64_t QP = qbefore + qi - qv;
-    const uint32_t CP = cbefore + ci - c;
-    s_cnt[tid] = CP;  // own slot: read above by this thread only
-    s_q[tid] = (uint64_t)QP;
-    int ovf = (Q > (int64_t)R && QP + qv > (int64_t)R) ? tid : WT_NB;
-    ovf = wave_min_int(ovf);
-    if (lane == 0) s_w[24 + wv] = (uint64_t)(uint32_t)ovf;
-    __syncthreads();
-    int b_ov = WT_NB;
-#pragma unroll
-    for (int i = 0; i < WT_WAVES; ++i) b_ov = min(b_ov, (int)(uint32_t)s_w[24 + i]);
-    NSG_STAMP(p, b, tid, 6);
-    // inclusive prefix of bucket bk (the last bucket: Q)
-    auto incl_of = [&](int bk) __attribute__((always_inline)) -> int64_t {
-        return bk + 1 < WT_NB ? (int64_t)s_q[bk + 1] : Q;
-    };
-    // ---- gather the kept members of bucket `bk` (block-uniform) into s_mem / s_memq; returns their count
-    auto gather = [&](int bk) __attribute__((always_inline)) -> int {
-        if (tid == 0) s_ctr[0] = 0u;
-        __syncthreads();
-        for_each([&](float xv, int i) __attribute__((always_inline)) {
-            if (!(xv >= vk) || (int)bucket_of(xv) != bk) return;
-            const uint32_t at = atomicAdd(&s_ctr[0], 1u);
-            if (at < (uint32_t)WT_GM) {
-                const double e = exp_canon(((double)xv - m) * p.inv_temp);
-                s_mem[at] = wkey(xv, seg_id(gj, i, p.V <= 65536));
-                s_memq[at] = (int64_t)__builtin_rint((e / E) * Rd);
-            }
-        });
-        __syncthreads();
-        return (int)s_ctr[0];
-    };
-    // wave 0: member `lane + 64 j` of the gathered bucket: key, q, rank among the members, cum = inclusive prefix
-    struct Mem {
-        uint64_t key[WT_GM / WAVE];
-        int64_t q[WT_GM / WAVE], cum[WT_GM / WAVE];
-        int rank[WT_GM / WAVE];
-    };
-    auto resolve = [&](int bk, int nm, Mem& mm) __attribute__((always_inline)) {
-#pragma unroll
-        for (int j = 0; j < WT_GM / WAVE; ++j) {
-            const int i = lane + WAVE * j;
-            mm.key[j] = i < nm ? s_mem[i] : 0ull;
-            mm.q[j] = i < nm ? s_memq[i] : 0;
-            mm.rank[j] = 0;
-            mm.cum[j] = 0;
-        }
-        for (int o = 0; o < nm; ++o) {
-            const uint64_t ko = s_mem[o];
-            const int64_t qo = s_memq[o];
-#pragma unroll
-            for (int j = 0; j < WT_GM / WAVE; ++j) {
-                mm.rank[j] += ko > mm.key[j] ? 1 : 0;
-                mm.cum[j] += ko >= mm.key[j] ? qo : 0;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < WT_GM / WAVE; ++j) mm.cum[j] += (int64_t)s_q[bk];
-    };
-    // ---- overfill: kp = first rank whose cum exceeds R (b_ov == WT_NB: none, kp = k0)
-    int kp = k0, kp_local = WT_GM + 1;
-    int64_t cumkp = Q;
-    if (b_ov < WT_NB) {
-        const int nm = gather(b_ov);
-        if (nm > WT_GM) {  // a crowded bucket (ties, skewed rows): counted like the LDS sort's bitonic fallback
-            if (tid == 0 && p.counters) atomicAdd(&p.counters[4 * (b & (NS_COUNTER_SHARDS - 1)) + 3], 1ull);
-            wtail_defer<T>(p, wsb, b, gv, gj, n, xt, keys_out, count, cap, todo, false, s_ctr, s_top);
-            return;
-        }
-        if (wv == 0) {
-            Mem mm;
-            resolve(b_ov, nm, mm);
-            int kl = WT_GM + 1;
-#pragma unroll
-            for (int j = 0; j < WT_GM / WAVE; ++j)
-                if (lane + WAVE * j < nm && mm.cum[j] > (int64_t)R) kl = min(kl, mm.rank[j]);
-            kl = wave_min_int(kl);
-            int64_t cprev = (int64_t)s_q[b_ov];
-#pragma unroll
-            for (int j = 0; j < WT_GM / WAVE; ++j) {
-                const uint64_t mp = ballot(lane + WAVE * j < nm && mm.rank[j] == kl - 1);
-                if (mp) cprev = (int64_t)readlane_u64((uint64_t)mm.cum[j], __builtin_ctzll(mp));
-            }
-            if (lane == 0) {
-                s_res[0] = kl;
-                s_res[1] = cprev;
-            }
-        }
-        __syncthreads();
-        kp_local = (int)s_res[0];
-        kp = (int)s_cnt[b_ov] + kp_local;
-        cumkp = s_res[1];
-    }
-    const int64_t shift = (int64_t)R - cumkp + (int64_t)st.lo;
-    // ---- the searched bucket: encode, the first bucket (<= b_ov) whose inclusive cum + shift exceeds the payload
-    // index; decode, the token's bucket (it must lie before the overfill point)
-    uint64_t idx = 0ull;
-    int bsel;
-    if (!DECODE) {
-        if (wv == 0) {
-            idx = payload_window(p, b, st.bit_pos);
-            int bl = WT_NB;
-#pragma unroll
-            for (int j = 0; j < WT_NB / WAVE; ++j) {
-                const int bk = lane * (WT_NB / WAVE) + j;
-                if (bk <= b_ov && bk < WT_NB && bl == WT_NB) {
-                    const int64_t inc = bk == b_ov ? cumkp : incl_of(bk);
-                    if ((uint64_t)(inc + shift) > idx) bl = bk;
-                }
-            }
-            bl = wave_min_int(bl);
-            if (lane == 0) {
-                s_res[2] = bl;
-                s_res[3] = (int64_t)idx;
-            }
-        }
-        __syncthreads();
-        bsel = (int)s_res[2];
-        idx = (uint64_t)s_res[3];
-    } else {
-        bsel = (int)bucket_of(xtok);
-    }
-    if (bsel >= WT_NB || bsel > b_ov) {  // encode range error, or a decode token past the overfill point
-        wtail_defer<T>(p, wsb, b, gv, gj, n, xt, keys_out, count, cap, todo, false, s_ctr, s_top);
-        return;
-    }
-    int nm = 0;
-    if (bsel != b_ov) {
-        nm = gather(bsel);
-    } else {
-        nm = (int)s_ctr[0];  // still gathered
-    }
-    if (nm > WT_GM) {
-        if (tid == 0 && p.counters) atomicAdd(&p.counters[4 * (b & (NS_COUNTER_SHARDS - 1)) + 3], 1ull);
-        wtail_defer<T>(p, wsb, b, gv, gj, n, xt, keys_out, count, cap, todo, false, s_ctr, s_top);
-        return;
-    }
-    int found = 0;
-    if (wv == 0) {
-        Mem mm;
-        resolve(bsel, nm, mm);
-        int rl = WT_GM + 1;
-#pragma unroll
-        for (int j = 0; j < WT_GM / WAVE; ++j) {
-            const bool valid = lane + WAVE * j < nm && (bsel != b_ov || mm.rank[j] < kp_local);
-            const bool hit = DECODE ? (valid && mm.key[j] == kt) : (valid && (uint64_t)(mm.cum[j] + shift) > idx);
-            if (hit) rl = min(rl, mm.rank[j]);
-        }
-        rl = wave_min_int(rl);
-        int64_t cum_sel = 0, q_sel = 0;
-        uint64_t key_sel = 0ull;
-#pragma unroll
-        for (int j = 0; j < WT_GM / WAVE; ++j) {
-            const uint64_t mh = ballot(lane + WAVE * j < nm && mm.rank[j] == rl);
-            if (mh) {
-                const int src = __builtin_ctzll(mh);
-                cum_sel = (int64_t)readlane_u64((uint64_t)mm.cum[j], src);
-                q_sel = (int64_t)readlane_u64((uint64_t)mm.q[j], src);
-                key_sel = readlane_u64(mm.key[j], src);
-            }
-        }
-        found = rl <= WT_GM;
-        if (found && lane == 0) {
-            const int sel = (int)s_cnt[bsel] + rl;
-            const RowStats rs{0.0, 0.0, 0.0};
-            wide_finish<DECODE>(p, b, st, k0, kp, sel, false, w.S_fast, sel > 0 ? cum_sel - q_sel : 0, cum_sel, shift,
-                                key_sel, m, rs, 0.0, false);
-        }
-        if (lane == 0) s_res[4] = found;
-    }
-    __syncthreads();
-    if (!s_res[4]) wtail_defer<T>(p, wsb, b, gv, gj, n, xt, keys_out, count, cap, todo, false, s_ctr, s_top);
-    NSG_STAMP(p, b, tid, 8);
-    NSG_STAMP_RT(p, b, tid, 10);
-}
-
-// The streams the tail kernel handed on (todo): up to FAST_NL collected keys are sorted in LDS and finished by
-// fast_tail (the exact row sum in the workgroup when needed); its own hand-offs (errors, non-finite rows) and the
-// longer segments (flat rows: pad stays set, the device-wide sort) go on to wide_cdf_kernel through todo2.  A
-// grid-stride loop over the list, so the launch does not depend on how many there are.
-template <typename T, bool DECODE>
-__global__ __launch_bounds__(FAST_THREADS) void wide_wlist_kernel(StepParams p, WideStat* ws, uint64_t* keys_in,
-                                                                  uint64_t* keys_out, const unsigned int* count,
-                                                                  int cap, const unsigned int* todo,
-                                                                  unsigned int* todo2) {
-    __shared__ uint64_t s_keys[FAST_NL];
-    __shared__ uint64_t s_aux[FAST_NB / 2];
-    const unsigned int nt = todo[0];
-    for (unsigned int i = blockIdx.x; i < nt; i += gridDim.x) {
-        const int b = (int)todo[1 + i];
-        const int n = (int)count[b];
-        if (n >= 2 && n <= FAST_NL) {
-            const WideStat w = ws[b];
-            __syncthreads();
-            if (threadIdx.x == 0) ws[b].pad = 0u;  // sorted here, not by the device-wide sort
-            fast_tail<T, DECODE, true>(p, w, &ws[b], b, n, KeysFlat{keys_out + (int64_t)b * cap, n}, keys_in, cap,
-                                       todo2, s_keys, s_aux);
-        } else if (threadIdx.x == 0) {
-            todo2[1 + atomicAdd(&todo2[0], 1u)] = (unsigned int)b;
-        }
-        __syncthreads();
-    }
+    fast_tail<T, DECODE>(p, w, b, n, at, keys_out, cap, todo, s_keys, s_aux);
 }
 
 // ------------------------------------------------------------------------------------------ rank coder
@@ -3922,7 +2176,7 @@ int nsg_wide_alloc(ns_ctx* ctx) {
         hipMalloc((void**)&w.count, ctx->max_batch * sizeof(unsigned int)) != hipSuccess ||
         hipMalloc((void**)&w.begin, ctx->max_batch * sizeof(unsigned int)) != hipSuccess ||
         hipMalloc((void**)&w.end, ctx->max_batch * sizeof(unsigned int)) != hipSuccess ||
-        hipMalloc((void**)&w.todo, 2 * (ctx->max_batch + 1) * sizeof(unsigned int)) != hipSuccess ||
+        hipMalloc((void**)&w.todo, (ctx->max_batch + 1) * sizeof(unsigned int)) != hipSuccess ||
         hipMalloc((void**)&w.stat, ctx->max_batch * sizeof(nsg::WideStat)) != hipSuccess)
         return NS_ERR_HIP;
     size_t bytes = 0;
@@ -3952,60 +2206,15 @@ void nsg_wide_free(ns_ctx* ctx) {
     w = NsgWide();
 }
 
-#ifndef NSG_WIDE_V2
-#define NSG_WIDE_V2 0  // 1: stream + tail kernels (round-4 experiment, measured slower: DESIGN.md §4 wide path)
-#endif
 template <typename T, bool DECODE>
 static bool wide_launch_t(ns_ctx* ctx, const nsg::StepParams& p, hipStream_t s) {
     NsgWide& w = ctx->wide;
     const int B = p.B;
-    static const int v2 = [] {
-        const char* e = getenv("NSG_WIDE_V2");
-        return e ? atoi(e) : NSG_WIDE_V2;
-    }();
-    if (v2 && !p.sample && !p.stats) {
-        // v2 = 1: stream kernel (wave per stream, 8 KiB buffers) + tail kernel; v2 = 2: wave per stream with the
-        // tail in the same wave (32 KiB buffers), the tail kernel only for the streams whose buffer overflowed.
-        // Only the streams the tails hand on are sorted and listed.
-        unsigned int* todo2 = w.todo + ctx->max_batch + 1;
-        if (v2 == 2) {
-            if (hipMemsetAsync(w.todo, 0, sizeof(unsigned int), s) != hipSuccess) return false;
-            hipLaunchKernelGGL((nsg::wide_wave_kernel<T, DECODE>), dim3(B), dim3(nsg::WAVE), 0, s, p, w.stat,
-                               w.keys_in, w.keys_out, w.count, w.cap, w.todo, todo2);
-        } else {
-            hipLaunchKernelGGL((nsg::wide_stream_kernel<T, DECODE>), dim3((B + nsg::WS_WAVES - 1) / nsg::WS_WAVES),
-                               dim3(nsg::WS_WAVES * nsg::WAVE), 0, s, p, w.stat, w.keys_in, w.count, w.cap, w.todo,
-                               todo2);
-        }
-        hipLaunchKernelGGL((nsg::wide_wtail_kernel<T, DECODE>), dim3(B), dim3(nsg::WT_THREADS), 0, s, p, w.stat,
-                           w.keys_in, w.keys_out, w.count, w.cap, w.todo);
-        hipLaunchKernelGGL((nsg::wide_wlist_kernel<T, DECODE>), dim3(B < 512 ? B : 512), dim3(nsg::FAST_THREADS), 0, s,
-                           p, w.stat, w.keys_in, w.keys_out, w.count, w.cap, w.todo, todo2);
-        hipLaunchKernelGGL(nsg::wide_offsets_kernel, dim3((B + 255) / 256), dim3(256), 0, s, B, w.cap, w.stat,
-                           w.count, w.begin, w.end, 0xFFFFFFFFu, nullptr);
-        size_t bytes = w.sort_tmp_bytes;
-        if (rocprim::segmented_radix_sort_keys_desc(w.sort_tmp, bytes, w.keys_out, w.keys_in,
-                                                    (unsigned int)((size_t)B * w.cap), (unsigned int)B, w.begin,
-                                                    w.end, 0, 49, s) != hipSuccess)
-            return false;
-        hipLaunchKernelGGL((nsg::wide_cdf_kernel<T, DECODE>), dim3(B < 256 ? B : 256), dim3(nsg::WIDE_THREADS), 0, s,
-                           p, w.stat, w.keys_in, w.count, w.cap, todo2);
-        return hipGetLastError() == hipSuccess;
-    }
     if (hipMemsetAsync(w.todo, 0, sizeof(unsigned int), s) != hipSuccess) return false;
-#if NSG_WIDE_ONEPASS
     hipLaunchKernelGGL((nsg::wide_onepass_kernel<T, DECODE>), dim3(B), dim3(nsg::FAST_THREADS), 0, s, p, w.stat,
                        w.keys_in, w.keys_out, w.count, w.cap, w.todo);
-#if NSG_WIDE_SPLIT
-    hipLaunchKernelGGL((nsg::wide_tail_kernel<T, DECODE>), dim3(B), dim3(nsg::FAST_THREADS), 0, s, p, w.stat,
-                       w.keys_in, w.keys_out, w.count, w.cap, w.todo);
-#endif
-#else
-    hipLaunchKernelGGL((nsg::wide_scan_kernel<T, DECODE>), dim3(B), dim3(nsg::FAST_THREADS), 0, s, p, w.stat,
-                       w.keys_in, w.keys_out, w.count, w.cap, w.todo);
-#endif
     hipLaunchKernelGGL(nsg::wide_offsets_kernel, dim3((B + 255) / 256), dim3(256), 0, s, B, w.cap, w.stat,
-                       w.count, w.begin, w.end, (unsigned int)nsg::FAST_NL, nullptr);
+                       w.count, w.begin, w.end, (unsigned int)nsg::FAST_NL);
     size_t bytes = w.sort_tmp_bytes;
     if (rocprim::segmented_radix_sort_keys_desc(w.sort_tmp, bytes, w.keys_in, w.keys_out,
                                                 (unsigned int)((size_t)B * w.cap), (unsigned int)B, w.begin,
@@ -4026,7 +2235,7 @@ static bool rank_launch_t(ns_ctx* ctx, const nsg::StepParams& p, hipStream_t s) 
     hipLaunchKernelGGL((nsg::wide_collect_kernel<T>), dim3(nchunk, B), dim3(256), 0, s, p, w.stat, w.keys_in,
                        w.count, w.cap);
     hipLaunchKernelGGL(nsg::wide_offsets_kernel, dim3((B + 255) / 256), dim3(256), 0, s, B, w.cap, w.stat,
-                       w.count, w.begin, w.end, 0u, nullptr);
+                       w.count, w.begin, w.end, 0u);
     size_t bytes = w.sort_tmp_bytes;
     if (rocprim::segmented_radix_sort_keys_desc(w.sort_tmp, bytes, w.keys_in, w.keys_out,
                                                 (unsigned int)((size_t)B * w.cap), (unsigned int)B, w.begin,
@@ -4046,7 +2255,7 @@ static bool rank64_launch_t(ns_ctx* ctx, const nsg::StepParams& p, hipStream_t s
     hipLaunchKernelGGL(nsg::rank64_collect_kernel, dim3(nchunk, B), dim3(256), 0, s, p, w.stat, w.keys_in, w.vals_in,
                        w.count, w.cap);
     hipLaunchKernelGGL(nsg::wide_offsets_kernel, dim3((B + 255) / 256), dim3(256), 0, s, B, w.cap, w.stat,
-                       w.count, w.begin, w.end, 0u, nullptr);
+                       w.count, w.begin, w.end, 0u);
     size_t bytes = w.sort_tmp_bytes;
     if (rocprim::segmented_radix_sort_pairs_desc(w.sort_tmp, bytes, w.keys_in, w.keys_out, w.vals_in, w.vals_out,
                                                  (unsigned int)((size_t)B * w.cap), (unsigned int)B, w.begin, w.end,

@@ -1,6 +1,6 @@
 """Time the wide path (api default quality: precision 16, topk 50,000, temp 1.0) at B streams on resident
-3*N(0,1) logits, one JSON line per dtype.  NSG_WIDE_V2=0/1 (read once per process) picks the one-pass kernel or
-the stream + tail kernels.  Usage: python tools/wide_probe.py [--batch 4096] [--steps 20] [--dtype f32 f16]"""
+3*N(0,1) logits, one JSON line per dtype.  Usage: python tools/wide_probe.py [--batch 4096] [--steps 20]
+[--dtype f32 f16]"""
 import argparse
 import json
 import os
@@ -55,7 +55,7 @@ def main():
         ntok = int(sess.fields()["ntokens"].astype("int64").sum()) - nt0
         esz = 4 if dt == "f32" else 2
         alg = B * (V * esz + 76)
-        print(json.dumps({"dtype": dt, "v2": os.environ.get("NSG_WIDE_V2"), "B": B, "ms_per_step": ms,
+        print(json.dumps({"dtype": dt, "B": B, "ms_per_step": ms,
                           "frac": alg / (ms / 1e3) / 1e9 / 8000.0, "tokens": ntok,
                           "exact_per_tok": (c1[0] - c0[0]) / max(ntok, 1),
                           "sweeps_per_tok": (c1[1] - c0[1]) / max(ntok, 1),
