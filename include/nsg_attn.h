@@ -63,7 +63,12 @@ int ns_decode_attention_prefix(const void* d_qkv, int64_t qkv_stride, void* d_k_
  * elements): half the HBM bytes of the fp16 cache.  The new token's k/v are quantised (saturated to +-448,
  * round to nearest even) before they are stored and used.  q, scores and the softmax stay fp16/fp32; rows
  * are split by key count only (64-row chunks), so the output is batch-invariant too.  An opt-in numerics
- * mode: logits differ from the fp16 cache's at the fp8 quantisation level. */
+ * mode: logits differ from the fp16 cache's at the fp8 quantisation level.
+ * Non-finite k/v (every entry point that converts: this one, ns_decode_attention_ex / _paged / _paged_chunk with
+ * NS_KV_FP8, the page store of ns_seq_attention_ragged, ns_quantize_fp8): +-inf saturate to +-448, -0 keeps its sign,
+ * and a NaN is stored as an e4m3 NaN byte (0x7F or 0xFF, both NaN to every reader) -- a poisoned row (the NaN rows
+ * below, NaN hidden rows of an out-of-range token id) stays NaN in the cache, so every later step of that stream
+ * gives NaN output rows, as with the fp16 cache, and no other stream is affected. */
 int ns_decode_attention_fp8(const void* d_qkv, int64_t qkv_stride, void* d_k_cache, void* d_v_cache,
                             int64_t cache_b_stride, int64_t cache_h_stride, int64_t cache_chunk_stride,
                             const void* d_k_prefix, const void* d_v_prefix, int64_t prefix_h_stride, int T0, int B,

@@ -79,8 +79,8 @@ __device__ __forceinline__ int att_split(int Lk) {
 
 // K/V storage formats.  A lane holds DPL consecutive dims of one key row, LPR lanes a row, RPI rows per 16-byte
 // wave-load, NI wave-loads per 32-row chunk.  The fp16 format is the reference configuration; the fp8 one
-// (OCP e4m3fn, saturated to +-448, round to nearest even; opt-in) halves the cache bytes the HBM-bound decode
-// reads.  q stays fp16 either way; scores and the softmax run in fp32.
+// (OCP e4m3fn, saturated to +-448, round to nearest even, NaN kept as the NaN byte; opt-in) halves the cache bytes the
+// HBM-bound decode reads.  q stays fp16 either way; scores and the softmax run in fp32.
 struct FmtF16 {
     static constexpr int DPL = 8, LPR = 8, RPI = 8, NI = 4;
     typedef _Float16 Elem;
@@ -94,12 +94,21 @@ struct FmtF16 {
     static __device__ __forceinline__ void unpack(Raw v, float* f) { unpack8(v, f); }
 };
 
+// Saturation to +-448 that keeps a NaN: ordered comparisons are false for NaN, so it passes through to the
+// conversion and becomes the e4m3 NaN byte.  (fminf(fmaxf(x, -448), 448) compiles to one v_med3_f32, which returns
+// -448 for a NaN operand: a poisoned k/v row -- NaN hidden rows of a bad token id, include/nsg_attn.h -- was stored
+// as finite -448s and the stream went on with finite, wrong logits.  +-inf saturate, -0 keeps its sign.)
+__device__ __forceinline__ float sat_fp8(float x) {
+    x = x > 448.0f ? 448.0f : x;
+    return x < -448.0f ? -448.0f : x;
+}
+
 __device__ __forceinline__ uint32_t pack4_fp8(float a, float b, float c, float d) {
     // saturate first: the conversion itself does not clamp, and e4m3fn has no infinity
-    a = fminf(fmaxf(a, -448.0f), 448.0f);
-    b = fminf(fmaxf(b, -448.0f), 448.0f);
-    c = fminf(fmaxf(c, -448.0f), 448.0f);
-    d = fminf(fmaxf(d, -448.0f), 448.0f);
+    a = sat_fp8(a);
+    b = sat_fp8(b);
+    c = sat_fp8(c);
+    d = sat_fp8(d);
     int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
     w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
     return (uint32_t)w;
