@@ -860,6 +860,18 @@ def rank_quality(quality) -> "_lib.NsRankQuality":
                               q.get("prob_temp", 0.0))
 
 
+def _rank_trace_rows(trace, B: int) -> np.ndarray:
+    """A rank session's last-step trace as a structured host array: ``k`` the support size n, ``kprime`` the capacity
+    c = floor(log2 n), ``sel`` the rank, ``n`` the bits taken (encode) or kept (decode), ``token``, ``S``.  A stream
+    that took no step in the launch (finished, inactive or in error) keeps its previous row."""
+    if trace is None:
+        raise ConfigurationError("the session's trace is off: call enable_trace() first")
+    raw = trace.cpu().numpy()
+    w = raw.view(np.int32).reshape(B, 8)
+    return np.rec.fromarrays([w[:, 0], w[:, 1], w[:, 2], w[:, 3], w[:, 4], raw[:, 3].view(np.float64)],
+                             names="k,kprime,sel,n,token,S")
+
+
 class RankEncodeSession:
     """B payloads (bytes) encoded by the src rank coder (``codec/arithmetic.py:122-168``), one launch per
     token; :meth:`consumed` is the reference's ``state["history"]`` per stream."""
@@ -885,13 +897,22 @@ class RankEncodeSession:
         self.out_token = torch.zeros(self.B, dtype=torch.int32, device=dev)
         self.hist = torch.full((self.B, cap), -1, dtype=torch.int32, device=dev)
         self.cons = torch.zeros((self.B, cap), dtype=torch.int32, device=dev)
+        self.trace = None
+
+    def enable_trace(self):
+        """Have every step write its ``ns_step_trace`` row per stream (see :func:`_rank_trace_rows`)."""
+        self.trace = _state_tensor(self.B, self.state.device)
+        return self.trace
+
+    def trace_rows(self) -> np.ndarray:
+        return _rank_trace_rows(self.trace, self.B)
 
     def step(self, logits):
         logits = _rank_rows(self.ctx, self.B, logits, self.q)
         rc = _lib.lib().ns_rank_encode_step(
             self.ctx._h, _ptr(logits), logits.stride(0), self.B, _ptr(self.payload), self.payload.stride(0),
             _ptr(self.nbits), _ptr(self.state), _ptr(self.out_token), _ptr(self.hist), _ptr(self.cons),
-            self.hist.shape[1], self.temp, ctypes.byref(self.q), ctypes.c_void_p(0), 0, _stream_handle())
+            self.hist.shape[1], self.temp, ctypes.byref(self.q), _ptr(self.trace), 0, _stream_handle())
         self.ctx.check(rc, "ns_rank_encode_step")
         return self.out_token
 
@@ -950,6 +971,15 @@ class RankDecodeSession:
         self.state = _state_tensor(self.B, dev)
         ctx.check(_lib.lib().ns_init_state(ctx._h, _ptr(self.state), self.B, _stream_handle()), "ns_init_state")
         self.t = 0
+        self.trace = None
+
+    def enable_trace(self):
+        """As :meth:`RankEncodeSession.enable_trace`; ``n`` is the number of bits kept of the token's rank."""
+        self.trace = _state_tensor(self.B, self.state.device)
+        return self.trace
+
+    def trace_rows(self) -> np.ndarray:
+        return _rank_trace_rows(self.trace, self.B)
 
     def step(self, logits) -> None:
         t = self.t
@@ -957,7 +987,7 @@ class RankDecodeSession:
         rc = _lib.lib().ns_rank_decode_step(
             self.ctx._h, _ptr(logits), logits.stride(0), self.B, _ptr(self.tok[t]), _ptr(self.keep[t]),
             _ptr(self.act[t]), _ptr(self.state), _ptr(self.out_bits), self.out_stride, self.temp,
-            ctypes.byref(self.q), ctypes.c_void_p(0), 0, _stream_handle())
+            ctypes.byref(self.q), _ptr(self.trace), 0, _stream_handle())
         self.ctx.check(rc, "ns_rank_decode_step")
         self.t += 1
 

@@ -96,12 +96,16 @@ def lib() -> ctypes.CDLL:
         L.or_rank_step.argtypes = [fp, ctypes.c_int, ctypes.c_double, ctypes.POINTER(OrRankQuality), ctypes.c_int,
                                    u8p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(OrState),
                                    i32p, i32p, u8p, i32p]
+        L.or_rank_step_n.restype = ctypes.c_int
+        L.or_rank_step_n.argtypes = L.or_rank_step.argtypes + [ctypes.POINTER(ctypes.c_int64)]
         L.or_np_sum.restype = ctypes.c_double
         L.or_np_sum.argtypes = [dp, ctypes.c_int64]
         L.or_rank_step64.restype = ctypes.c_int
         L.or_rank_step64.argtypes = [dp, ctypes.c_int, i32p, ctypes.c_int, ctypes.POINTER(OrRankQuality), ctypes.c_int,
                                      u8p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(OrState),
                                      i32p, i32p, u8p, i32p]
+        L.or_rank_step64_n.restype = ctypes.c_int
+        L.or_rank_step64_n.argtypes = L.or_rank_step64.argtypes + [ctypes.POINTER(ctypes.c_int64)]
         L.or_encode_batch.restype = ctypes.c_int
         L.or_encode_batch.argtypes = [fp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, i32p, ctypes.c_int,
                                       ctypes.c_double, ctypes.c_int, ctypes.c_int, u8p, ctypes.c_int64,
@@ -321,6 +325,44 @@ def rank_decode_stream(row_fn: RowFn, tokens: Sequence[int], consumed: Sequence[
         if rc != OR_OK:
             raise RuntimeError(f"oracle rank decode step {t} failed rc={rc}")
     return out.tobytes()[: nbits // 8]
+
+
+def rank_step_n(row: np.ndarray, st: OrState, *, temp: float, quality, payload: np.ndarray = None, nbits: int = 0,
+                token: int = None, keep: int = 0, out_bits: np.ndarray = None) -> Tuple[int, int, int, int, int]:
+    """One ``or_rank_step_n`` on a logit row: encode (``payload`` bytes, ``nbits``) when ``token`` is None, else the
+    decode of ``token`` (``keep`` bits into ``out_bits``).  Returns (rc, token, consumed, capacity, n): n is the
+    support size of steps R1-R3, of which the coder itself uses only c = floor(log2 n)."""
+    x = np.ascontiguousarray(row, dtype=np.float32)
+    rq = quality if isinstance(quality, OrRankQuality) else rank_quality(quality)
+    tok, c, cap, n = ctypes.c_int32(-1), ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int64(-1)
+    if token is None:
+        rc = lib().or_rank_step_n(_fptr(x), x.size, 1.0 / float(temp), ctypes.byref(rq), 0, _u8(payload), int(nbits),
+                                  -1, 0, ctypes.byref(st), ctypes.byref(tok), ctypes.byref(c), None,
+                                  ctypes.byref(cap), ctypes.byref(n))
+        return rc, tok.value, c.value, cap.value, n.value
+    rc = lib().or_rank_step_n(_fptr(x), x.size, 1.0 / float(temp), ctypes.byref(rq), 1, None, 0, int(token),
+                              int(keep), ctypes.byref(st), None, None, _u8(out_bits), ctypes.byref(cap),
+                              ctypes.byref(n))
+    return rc, int(token), min(int(keep), cap.value), cap.value, n.value
+
+
+def rank_step64_n(dist, st: OrState, *, quality, payload: np.ndarray = None, nbits: int = 0, token: int = None,
+                  keep: int = 0, out_bits: np.ndarray = None) -> Tuple[int, int, int, int, int]:
+    """:func:`rank_step_n` over a provider's ProbDist (``or_rank_step64_n``; an ndarray by id or an ``{id: p}``
+    dict): (rc, token, consumed, capacity, n)."""
+    v, ids, is_dict = dist_arrays(dist)
+    rq = quality if isinstance(quality, OrRankQuality) else rank_quality(quality)
+    tok, c, cap, n = ctypes.c_int32(-1), ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int64(-1)
+    vp = v.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    idp = _i32(ids) if ids is not None else None
+    if token is None:
+        rc = lib().or_rank_step64_n(vp, v.size, idp, int(is_dict), ctypes.byref(rq), 0, _u8(payload), int(nbits), -1,
+                                    0, ctypes.byref(st), ctypes.byref(tok), ctypes.byref(c), None, ctypes.byref(cap),
+                                    ctypes.byref(n))
+        return rc, tok.value, c.value, cap.value, n.value
+    rc = lib().or_rank_step64_n(vp, v.size, idp, int(is_dict), ctypes.byref(rq), 1, None, 0, int(token), int(keep),
+                                ctypes.byref(st), None, None, _u8(out_bits), ctypes.byref(cap), ctypes.byref(n))
+    return rc, int(token), min(int(keep), cap.value), cap.value, n.value
 
 
 def np_sum(a: np.ndarray) -> float:
