@@ -133,11 +133,25 @@ int ns_decode_step(ns_ctx* ctx, const void* d_logits, int64_t ld, int B, const i
  * is_sent_finish).  The caller keeps it alive; NULL clears it. */
 int ns_set_sentence_end(ns_ctx* ctx, const uint8_t* d_table);
 
-/* Rank export for decode repair: when a later ns_decode_step finds stream b's received token outside the
- * kept top-k' (NS_ST_ERR_DIVERGE; the state is left unchanged so the step can be re-issued), the kernel
- * writes the kept ids in rank order to d_ranked[b*stride + i], i < k', followed by -1 (truncated at
- * stride).  The host runs the reference's BPE-repair heuristics on them (code_base/arithmetic.py:300-342)
- * and re-issues the step with the repaired token.  d_ranked is a DEVICE int32 array; NULL switches it off. */
+/* Divergence contract of ns_decode_step (single-pass and wide path alike).  A received token that is not one of
+ * the ids at ranks 0 .. k'-1 of the step's CDF -- an id at rank >= k' (k' <= k: the overfill trim counts), a banned
+ * id, an id outside [0, vocab) (never used as a row index), an id whose -inf logit the cutoff drops -- diverges:
+ *   - the stream's lo, hi, bit_pos, ntokens and every byte of its d_out_bits row are left as they were; the only
+ *     change is flags |= NS_ST_ERR_DIVERGE | NS_ST_DONE.  d_trace[b], when given, is (k, k', -1, -1, -1).
+ *   - a stream with NS_ST_DONE set is skipped by every later step (state, bits, trace and export untouched), so the
+ *     host must clear BOTH flags before it re-issues the step; with d_active set for that stream only, the
+ *     re-issued step touches no other stream.
+ *   - a non-finite row (a NaN or +inf logit) is NS_ST_ERR_RANGE | NS_ST_DONE whatever the token, with the state and
+ *     the bits unchanged as well, and is NOT a divergence: nothing is exported for it.
+ *
+ * Rank export for decode repair: while a d_ranked array is registered, a step that flags stream b
+ * NS_ST_ERR_DIVERGE -- and no other step: not a successful one, not a skipped stream, not NS_ST_ERR_RANGE --
+ * writes the kept ids in rank order to d_ranked[b*stride + i], i < min(k', stride), followed by -1 at index k' when
+ * k' < stride (so stride = k' gives k' ids and no terminator).  Nothing else of the array is written: no element
+ * past the terminator, no row of another stream.  The host runs the reference's BPE-repair heuristics on them
+ * (code_base/arithmetic.py:300-342) and re-issues the step with the repaired token.  d_ranked is a DEVICE int32
+ * array of max_batch * stride elements, stride >= 2 (NS_ERR_CONFIG otherwise); NULL switches the export off (the
+ * flags are set all the same). */
 int ns_set_rank_export(ns_ctx* ctx, int32_t* d_ranked, int stride);
 
 /* Statistics of the encode steps (code_base/arithmetic.py:193-199, returned by encode_arithmetic :217):

@@ -1430,7 +1430,9 @@ __global__ __launch_bounds__((NSPLIT > 1 ? NSPLIT : WPB) * WAVE, NSG_MIN_WAVES_P
         }
         if (sel < 0) {
             err = NS_ST_ERR_DIVERGE;
-            if (p.ranked) {  // export the ranked kept ids for the host's BPE repair (arithmetic.py:300-342)
+            // export the ranked kept ids for the host's BPE repair (arithmetic.py:300-342): on a divergence only,
+            // a non-finite row (NS_ST_ERR_RANGE below) has no ranking to export
+            if (p.ranked && !short_row && E > 0.0 && E <= 1.7976931348623157e308) {
                 int32_t* rk_out = p.ranked + (int64_t)b * p.ranked_stride;
 #pragma unroll
                 for (int s = 0; s < NSK; ++s) {

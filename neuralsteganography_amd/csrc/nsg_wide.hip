@@ -687,7 +687,9 @@ __device__ __forceinline__ void wide_cdf_stream(const StepParams& p, const WideS
     const int sel = block_min_int(sel_l, smi);
     if (sel == 0x7FFFFFFF) err = DECODE ? NS_ST_ERR_DIVERGE : NS_ST_ERR_RANGE;
     if (!(E > 0.0 && E <= 1.7976931348623157e308)) err = NS_ST_ERR_RANGE;  // non-finite logits: no valid CDF
-    if (DECODE && err && p.ranked) {  // ranked kept ids for the host's BPE repair (arithmetic.py:300-342)
+    // ranked kept ids for the host's BPE repair (arithmetic.py:300-342): on a divergence only, a non-finite row
+    // (NS_ST_ERR_RANGE) has no ranking to export
+    if (DECODE && err == NS_ST_ERR_DIVERGE && p.ranked) {
         int32_t* rk_out = p.ranked + (int64_t)b * p.ranked_stride;
         for (int i = tid; i < kp && i < p.ranked_stride; i += WIDE_THREADS) rk_out[i] = (int32_t)wkey_id(sk[i]);
         if (tid == 0 && kp < p.ranked_stride) rk_out[kp] = -1;
@@ -1116,7 +1118,7 @@ __device__ __forceinline__ void fast_tail(const StepParams& p, const WideStat& w
 #pragma unroll
     for (int i = 0; i < FAST_WAVES; ++i) sel = min(sel, s_k[i]);
     if (sel == 0x7FFFFFFF || !(E > 0.0 && E <= 1.7976931348623157e308)) {  // range / divergence error or
-        // non-finite logits: wide_cdf_kernel reports it (and the ranked export)
+        // non-finite logits: wide_cdf_kernel reports it (and, for a divergence, writes the ranked export)
         defer();
         return;
     }

@@ -79,6 +79,8 @@ def lib() -> ctypes.CDLL:
         L.or_decode_step.argtypes = [fp, ctypes.c_int, i32p, ctypes.c_int, ctypes.c_double, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_int32, ctypes.c_int, ctypes.POINTER(OrState), u8p,
                                      ctypes.POINTER(OrTrace)]
+        L.or_decode_step_kept.restype = ctypes.c_int
+        L.or_decode_step_kept.argtypes = L.or_decode_step.argtypes + [i32p, ctypes.c_int]
         L.or_row_sum.restype = ctypes.c_double
         L.or_row_sum.argtypes = [fp, ctypes.c_int, i32p, ctypes.c_int, ctypes.c_double, ctypes.c_double]
         dp = ctypes.POINTER(ctypes.c_double)
@@ -173,7 +175,21 @@ def decode_step(row: np.ndarray, st: OrState, token: int, is_last: bool, out_bit
     return rc, tr
 
 
-RowFn = Callable[[int], np.ndarray]
+def decode_step_kept(row: np.ndarray, st: OrState, token: int, is_last: bool, out_bits: np.ndarray, *, banned,
+                     temp: float, precision: int, topk: int) -> Tuple[int, OrTrace, List[int]]:
+    """:func:`decode_step` that also returns the ids of ranks ``0 .. k'-1`` in rank order (``or_step``'s own sorted
+    keys), whether the step succeeds or diverges: what ``ns_set_rank_export`` promises for a diverged stream."""
+    x = np.ascontiguousarray(row, dtype=np.float32)
+    b = np.ascontiguousarray(banned, dtype=np.int32)
+    tr = OrTrace()
+    kept = np.full(min(int(topk), x.size), -1, dtype=np.int32)  # k' <= min(topk, valid ids)
+    rc = lib().or_decode_step_kept(_fptr(x), x.size, _i32(b), b.size, 1.0 / float(temp), int(precision), int(topk),
+                                   int(token), int(bool(is_last)), ctypes.byref(st), _u8(out_bits), ctypes.byref(tr),
+                                   _i32(kept), kept.size)
+    return rc, tr, (kept[: tr.kprime].tolist() if rc in (OR_OK, OR_ERR_DIVERGE) else [])
+
+
+RowFn =Callable[[int], np.ndarray]
 
 
 def stats_summary(acc: np.ndarray, bits_consumed: int = None) -> dict:
