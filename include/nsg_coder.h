@@ -259,9 +259,25 @@ int ns_stream_quality_fill(int vocab, const int32_t* banned, int nbanned, double
  * row b (the calls' temp / topk arguments and the context's precision are ignored) and every host decision --
  * the rank-slot bucket, the split or wave-per-stream form, the sample -- follows k_max alone, so a captured step
  * stays valid whatever the rows hold.  Every row must have been filled with this k_max and K <= k_max.
- * k_max > ns_max_topk(dtype) (the wide path): NS_ERR_UNSUPPORTED.  ns_sample_step, the rank steps and
- * ns_token_probs return NS_ERR_CONFIG while a table is registered. */
+ * k_max > ns_max_topk(dtype) (the wide path): NS_ERR_UNSUPPORTED here, ns_set_stream_quality_wide takes it.
+ * ns_sample_step, the rank steps and ns_token_probs return NS_ERR_CONFIG while a table is registered. */
 int ns_set_stream_quality(ns_ctx* ctx, const ns_stream_quality* d_table, int k_max);
+
+/* The same registration without the k_max limit: rows of any topk in [1, k_max] in one call, k_max beyond
+ * ns_max_topk(dtype) included (the api default, topk 50,000, and the message->bits mode, topk 60,000).  The steps
+ * dispatch exactly as a call with topk = k_max and no table does: min(k_max, valid ids) > ns_max_topk(dtype) runs
+ * the wide chain, whose kernels read stream b's temp, topk, K and precision from row b (a row's K only shortens
+ * the ranks it looks at, so a row at or below ns_max_topk is served there too); otherwise -- a vocabulary that
+ * leaves at most ns_max_topk valid ids -- the single-pass kernel runs with the table as under
+ * ns_set_stream_quality, and no wide-path buffers are needed.  The wide chain needs the buffers of a context
+ * created with max_k > ns_max_topk(dtype).  The banned ids are known only at the step, so a context without them
+ * is refused here (NS_ERR_UNSUPPORTED) when no ban list could bring the valid ids down to the limit, i.e.
+ * k_max > ns_max_topk and vocab > ns_max_topk + NS_MAX_BANNED; otherwise the step itself returns
+ * NS_ERR_UNSUPPORTED when min(k_max, valid ids) > ns_max_topk.  NS_ERR_CONFIG for a null context, k_max < 1, a
+ * misaligned table or a NS_DTYPE_F64 context.  NULL clears the table (either entry clears what the other
+ * registered).  ns_sample_step, the rank steps and ns_token_probs return NS_ERR_CONFIG while a table is
+ * registered. */
+int ns_set_stream_quality_wide(ns_ctx* ctx, const ns_stream_quality* d_table, int k_max);
 
 /* Rare-event diagnostics, cumulative since ns_create: counters[0] = stream-steps that took the exact-sum
  * path, counters[1] = candidate-buffer overflow compactions, counters[2] = speculative-threshold misses

@@ -29,7 +29,7 @@ EXPORTS = ("ns_create", "ns_destroy", "ns_last_error", "ns_version", "ns_max_top
            "ns_init_state",
            "ns_encode_step", "ns_decode_step", "ns_set_sentence_end", "ns_set_stats", "ns_sample_step", "ns_set_rank_export",
            "ns_rank_encode_step", "ns_set_rank_rows", "ns_rank_decode_step", "ns_token_probs",
-           "ns_stream_quality_fill", "ns_set_stream_quality",
+           "ns_stream_quality_fill", "ns_set_stream_quality", "ns_set_stream_quality_wide",
            "ns_read_counters", "ns_decode_attention", "ns_decode_attention_dev", "ns_decode_attention_prefix",
            "ns_decode_attention_fp8", "ns_decode_attention_ex", "ns_quantize_fp8",
            "ns_score_rows", "ns_lm_head_score", "ns_lm_head_score_work_bytes",
@@ -135,6 +135,8 @@ def lib() -> ctypes.CDLL:
                                          ctypes.c_int, ctypes.c_int, ctypes.POINTER(NsStreamQuality)]
     L.ns_set_stream_quality.restype = ctypes.c_int
     L.ns_set_stream_quality.argtypes = [vp, vp, ctypes.c_int]
+    L.ns_set_stream_quality_wide.restype = ctypes.c_int
+    L.ns_set_stream_quality_wide.argtypes = [vp, vp, ctypes.c_int]
     L.ns_set_stats.restype = ctypes.c_int
     L.ns_set_stats.argtypes = [vp, vp]
     L.ns_sample_step.restype = ctypes.c_int

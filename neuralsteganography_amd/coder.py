@@ -164,15 +164,19 @@ def _check_quality(ctx: "CoderContext", B: int, quality: Optional[StreamQuality]
 
 
 class _table_registered:
-    """``ns_set_stream_quality`` around a call (None: nothing to do), cleared on exit like ``ns_set_stats``."""
+    """``ns_set_stream_quality`` around a call (None: nothing to do), cleared on exit like ``ns_set_stats``; a
+    ``k_max`` beyond the single-pass limit goes through ``ns_set_stream_quality_wide`` (the wide kernels read the
+    rows)."""
 
     def __init__(self, ctx: "CoderContext", table, k_max: int):
         self.ctx, self.table, self.k_max = ctx, table, k_max
 
     def __enter__(self):
         if self.table is not None:
-            self.ctx.check(_lib.lib().ns_set_stream_quality(self.ctx._h, _ptr(self.table), int(self.k_max)),
-                           "ns_set_stream_quality")
+            L = _lib.lib()
+            entry = L.ns_set_stream_quality_wide if int(self.k_max) > self.ctx.single_pass_limit \
+                else L.ns_set_stream_quality
+            self.ctx.check(entry(self.ctx._h, _ptr(self.table), int(self.k_max)), "ns_set_stream_quality")
 
     def __exit__(self, *exc):
         if self.table is not None and self.ctx._h:
@@ -214,7 +218,8 @@ class CoderContext:
         L = _lib.lib()
         vocab_valid = params.vocab - len({b for b in params.banned_ids() if 0 <= b < params.vocab})
         self.K = min(params.topk, vocab_valid)
-        self.wide = self.K > L.ns_max_topk(params.dtype_code)  # large top-k: multi-kernel wide path
+        self.single_pass_limit = int(L.ns_max_topk(params.dtype_code))
+        self.wide = self.K > self.single_pass_limit  # large top-k: multi-kernel wide path
         handle = L.ns_create(self.device, self.max_batch, params.vocab, max(1, self.K), params.precision,
                              params.dtype_code)
         if not handle:

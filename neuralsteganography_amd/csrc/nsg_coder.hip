@@ -1705,7 +1705,7 @@ static bool launch(ns_ctx* ctx, const nsg::StepParams& p, hipStream_t s) {
 
 extern "C" {
 
-const char* ns_version(void) { return "nsgcoder 0.31.2 gfx950"; }
+const char* ns_version(void) { return "nsgcoder 0.31.3 gfx950"; }
 
 int ns_set_split_max_batch(int max_batch) {
     const int prev = split_setting();
@@ -2108,7 +2108,8 @@ int ns_stream_quality_fill(int vocab, const int32_t* banned, int nbanned, double
     return NS_OK;
 }
 
-int ns_set_stream_quality(ns_ctx* ctx, const ns_stream_quality* d_table, int k_max) {
+// wide: ns_set_stream_quality_wide (k_max beyond the single-pass limit allowed)
+static int set_stream_quality(ns_ctx* ctx, const ns_stream_quality* d_table, int k_max, bool wide) {
     if (!ctx) return fail(ctx, NS_ERR_CONFIG, "ns_set_stream_quality: null context");
     if (!d_table) {
         ctx->quality = nullptr;
@@ -2119,13 +2120,29 @@ int ns_set_stream_quality(ns_ctx* ctx, const ns_stream_quality* d_table, int k_m
         return fail(ctx, NS_ERR_CONFIG, "ns_set_stream_quality: a NS_DTYPE_F64 context runs the rank coder only");
     if (k_max < 1 || ((uintptr_t)d_table & 7u) != 0u)
         return fail(ctx, NS_ERR_CONFIG, "ns_set_stream_quality: k_max must be positive and the table 8-byte aligned");
-    if (k_max > ns_max_topk(ctx->dtype))
-        return fail(ctx, NS_ERR_UNSUPPORTED,
-                    "ns_set_stream_quality: k_max beyond the single-pass limit (ns_max_topk): the wide path takes "
-                    "one quality per call");
+    if (k_max > ns_max_topk(ctx->dtype)) {
+        if (!wide)
+            return fail(ctx, NS_ERR_UNSUPPORTED,
+                        "ns_set_stream_quality: k_max beyond the single-pass limit (ns_max_topk): "
+                        "ns_set_stream_quality_wide takes such a table");
+        // without the wide buffers the call can still be served by the single-pass kernel when the bans of the step
+        // leave at most ns_max_topk valid ids (prepare() checks that); refused here only when no ban list could
+        if (!ctx->wide.keys_in && ctx->vocab > ns_max_topk(ctx->dtype) + NS_MAX_BANNED)
+            return fail(ctx, NS_ERR_UNSUPPORTED,
+                        "ns_set_stream_quality_wide: k_max beyond the single-pass limit (ns_max_topk) needs a context "
+                        "created with max_k beyond it (the wide-path buffers)");
+    }
     ctx->quality = d_table;
     ctx->q_kmax = k_max;
     return NS_OK;
+}
+
+int ns_set_stream_quality(ns_ctx* ctx, const ns_stream_quality* d_table, int k_max) {
+    return set_stream_quality(ctx, d_table, k_max, false);
+}
+
+int ns_set_stream_quality_wide(ns_ctx* ctx, const ns_stream_quality* d_table, int k_max) {
+    return set_stream_quality(ctx, d_table, k_max, true);
 }
 
 int ns_set_sentence_end(ns_ctx* ctx, const uint8_t* d_table) {

@@ -316,8 +316,9 @@ struct StepParams {
     ns_stream_state* state;
     ns_step_trace* trace;
     unsigned long long* counters;
-    // per-stream quality rows (ns_set_stream_quality), nullable: then P, topk, K, inv_temp, c32 and spec_j above
-    // hold for every stream.  With a table, K and spec_j above are those of the call's k_max (host decisions).
+    // per-stream quality rows (ns_set_stream_quality / ns_set_stream_quality_wide), nullable: then P, topk, K,
+    // inv_temp, c32 and spec_j above hold for every stream.  With a table, K and spec_j above are those of the call's
+    // k_max (host decisions).
     const ns_stream_quality* quality;
 };
 

@@ -17,8 +17,11 @@
 //   3. wide_cdf_kernel     (1024 threads/block, grid-stride over the work list): the general canonical tail --
 //                          cutoff, canonical sums (the exact row sum when the fast-sum interval is ambiguous),
 //                          rint, int64 scan, overfill, selection, interval update
-// Rank coder (ns_rank_*_step): wide_stats_kernel (wave per stream) -> wide_collect_kernel (blocks per chunk,
-// every valid id) -> the device-wide sort -> wide_rank_kernel.
+// With a stream quality table (ns_set_stream_quality_wide) steps 1 and 3 take stream b's temperature, topk, K and
+// precision from row b (row_quality, read once per stream); a row's K may be anything in [1, k_max] -- it only
+// shortens the ranks the cutoff looks at.  The launches follow the call's k_max alone.
+// Rank coder (ns_rank_*_step, scalar quality only): wide_stats_kernel (wave per stream) -> wide_collect_kernel
+// (blocks per chunk, every valid id) -> the device-wide sort -> wide_rank_kernel.
 // An id left out of the collection has e_i < S_lo/R <= S/R, i.e. p_i < 1/R for certain, so the first rank
 // below the cutoff lies inside the collected prefix or right after it.
 
@@ -241,13 +244,14 @@ __global__ void wide_offsets_kernel(int B, int cap, const WideStat* ws, const un
 
 // ------------------------------------------------------------------------------------------ canonical tail (list kernel)
 // the next P payload bits (LSB-first bytes) as an MSB-first integer, zero-padded past the end: one bit per lane
-// and a ballot (every lane of the wave must be active); the loads are independent, not a P-long chain
-__device__ __forceinline__ uint64_t payload_window(const StepParams& p, int b, int64_t bit_pos) {
+// and a ballot (every lane of the wave must be active); the loads are independent, not a P-long chain.  P: the
+// stream's precision (row_quality)
+__device__ __forceinline__ uint64_t payload_window(const StepParams& p, int b, int64_t bit_pos, int P) {
     const int lane = (int)(threadIdx.x & (WAVE - 1));
     const int64_t bp = bit_pos + lane;
     uint32_t bit = 0u;
-    if (lane < p.P && bp < p.nbits[b]) bit = (p.payload[(int64_t)b * p.payload_stride + (bp >> 3)] >> (bp & 7)) & 1u;
-    return __builtin_bitreverse64(ballot(bit != 0u)) >> (64 - p.P);
+    if (lane < P && bp < p.nbits[b]) bit = (p.payload[(int64_t)b * p.payload_stride + (bp >> 3)] >> (bp & 7)) & 1u;
+    return __builtin_bitreverse64(ballot(bit != 0u)) >> (64 - P);
 }
 
 // block helpers (1024 threads = 16 waves)
@@ -293,7 +297,8 @@ __device__ __forceinline__ double block_canonical_butterfly(double* sm64) {
 }
 
 template <typename T, int NT = WIDE_THREADS, int ROUND = WIDE_ROUND>
-__device__ double block_exact_row_sum(const StepParams& p, const char* rowc, double m, double* ebuf, double* sm64) {
+__device__ double block_exact_row_sum(const StepParams& p, const char* rowc, double m, double inv_temp, double* ebuf,
+                                      double* sm64) {
     // canonical order: id j -> lane (j>>2)&63, per-lane increasing; exps computed in parallel per round; the
     // next round's logits are loaded into registers before this round's ordered chain runs (a second LDS
     // buffer to overlap the chain with the next round's exps measured no faster).  NT threads, ROUND ids per
@@ -317,7 +322,7 @@ __device__ double block_exact_row_sum(const StepParams& p, const char* rowc, dou
             const int i = u * NT + (int)threadIdx.x;
             const int j = base + i;
             double e = 0.0;
-            if (j < p.V && !is_banned(p, j)) e = exp_canon(((double)(xv[u] + 0.0f) - m) * p.inv_temp);
+            if (j < p.V && !is_banned(p, j)) e = exp_canon(((double)(xv[u] + 0.0f) - m) * inv_temp);
             eb[i] = e;
         }
         if (base + ROUND < p.V) load_round(base + ROUND);
@@ -364,15 +369,15 @@ __device__ __forceinline__ double block_sum(double v, double* sm64) {
 
 // statistics fallback (block version of wave_row_stats): float64 exps against the true max
 template <typename T>
-__device__ RowStats block_row_stats(const StepParams& p, const char* rowc, double m, double* sm64) {
+__device__ RowStats block_row_stats(const StepParams& p, const char* rowc, double m, double inv_temp, double* sm64) {
     double s1 = 0.0, st = 0.0, at = 0.0;
     for (int j = threadIdx.x; j < p.V; j += WIDE_THREADS) {
         if (is_banned(p, j)) continue;
         const double d = (double)(Elem<T>::load1(rowc, j) + 0.0f) - m;
-        const double et = exp(d * p.inv_temp);
+        const double et = exp(d * inv_temp);
         s1 += exp(d);
         st += et;
-        at += et * (d * p.inv_temp);
+        at += et * (d * inv_temp);
     }
     s1 = block_sum(s1, sm64);
     st = block_sum(st, sm64);
@@ -411,12 +416,13 @@ __device__ double block_mass(int k, EOf e_of, double* sm64) {
     return mass_value(t);
 }
 
-// interval update, bit emit and state/statistics writes of one finished step (thread 0; both CDF kernels)
+// interval update, bit emit and state/statistics writes of one finished step (thread 0; both CDF kernels); P: the
+// stream's precision (row_quality)
 template <bool DECODE>
-__device__ __forceinline__ void wide_finish(const StepParams& p, int b, const ns_stream_state& st, int k, int kp, int sel, bool exact,
-                            double S_used, int64_t cum_m1, int64_t cum_sel, int64_t shift, uint64_t sel_key, double m,
-                            const RowStats& rs, double kl, bool want_stats) {
-    const int P = p.P;
+__device__ __forceinline__ void wide_finish(const StepParams& p, int P, int b, const ns_stream_state& st, int k,
+                                            int kp, int sel, bool exact, double S_used, int64_t cum_m1,
+                                            int64_t cum_sel, int64_t shift, uint64_t sel_key, double m,
+                                            const RowStats& rs, double kl, bool want_stats) {
     const uint64_t mask = (P >= 64) ? ~0ull : ((1ull << P) - 1ull);
     const uint64_t new_lo = sel > 0 ? (uint64_t)(cum_m1 + shift) : st.lo;
     const uint64_t new_hi = (uint64_t)(cum_sel + shift);
@@ -476,6 +482,7 @@ __device__ __forceinline__ void wide_cdf_stream(const StepParams& p, const WideS
     __shared__ uint64_t sel_key;
     const WideStat w = ws[b];
     if (!w.active) return;
+    const RowQuality sq = row_quality(p, b);  // this stream's table row, or the call's scalars
     const int tid = threadIdx.x;
     const ns_stream_state st = p.state[b];
     const uint64_t* sk = keys_sorted + (int64_t)b * cap;
@@ -485,17 +492,17 @@ __device__ __forceinline__ void wide_cdf_stream(const StepParams& p, const WideS
         if (tid == 0) p.state[b].flags = st.flags | NS_ST_ERR_RANGE | NS_ST_DONE;
         return;
     }
-    const int Kc = min(nC, p.K);
+    const int Kc = min(nC, sq.K);
     const char* rowc = (const char*)p.logits + (int64_t)b * p.ld * (int64_t)sizeof(T);
     const double m = (double)wkey_val(sk[0]);
     const uint64_t R = st.hi - st.lo;
     const double Rd = (double)R;
     const double thr = 1.0 / Rd;
-    auto e_of = [&](int i) -> double { return exp_canon(((double)wkey_val(sk[i]) - m) * p.inv_temp); };
+    auto e_of = [&](int i) -> double { return exp_canon(((double)wkey_val(sk[i]) - m) * sq.inv_temp); };
     RowStats rs{0.0, 0.0, 0.0};
     const bool want_stats = !DECODE && p.stats != nullptr;
-    if (want_stats && !row_stats_from_stream(w.S_r, w.B_r, w.U_r, w.r, m, p.inv_temp, rs))
-        rs = block_row_stats<T>(p, rowc, m, sm64);
+    if (want_stats && !row_stats_from_stream(w.S_r, w.B_r, w.U_r, w.r, m, sq.inv_temp, rs))
+        rs = block_row_stats<T>(p, rowc, m, sq.inv_temp, sm64);
 
     if (!DECODE && p.sample) {  // sampler (oracle steps S2-S5): support, canonical E, 2^48 CDF, one draw
         int fl = Kc;
@@ -539,7 +546,7 @@ __device__ __forceinline__ void wide_cdf_stream(const StepParams& p, const WideS
             const double logE = log(E);
             for (int i = i0; i < i1; ++i) {
                 const double xi = (double)wkey_val(sk[i]) - m;
-                const double lq = xi * p.inv_temp - logE;
+                const double lq = xi * sq.inv_temp - logE;
                 const double q = e_of(i) / E;
                 kl += q * (lq - (xi - rs.lse1));
                 h += q * lq;
@@ -591,7 +598,7 @@ __device__ __forceinline__ void wide_cdf_stream(const StepParams& p, const WideS
             k0 = fb;
     }
     if (exact) {
-        const double S = block_exact_row_sum<T>(p, rowc, m, ebuf, sm64);
+        const double S = block_exact_row_sum<T>(p, rowc, m, sq.inv_temp, ebuf, sm64);
         S_used = S;
         int fb = Kc;
         for (int i = tid; i < Kc; i += WIDE_THREADS)
@@ -599,7 +606,7 @@ __device__ __forceinline__ void wide_cdf_stream(const StepParams& p, const WideS
         k0 = block_min_int(fb, smi);
     }
     int k = k0 < 2 ? 2 : k0;
-    if (k > p.topk) k = p.topk;
+    if (k > sq.topk) k = sq.topk;
 
     // ---- 2. E = sum_{i<k} e_i, order-free (exact limb sums, canonical step 6)
     const double E = block_mass(k, e_of, sm64);
@@ -663,7 +670,7 @@ __device__ __forceinline__ void wide_cdf_stream(const StepParams& p, const WideS
     int sel_l = 0x7FFFFFFF;
     uint32_t err = 0;
     if (!DECODE) {
-        const uint64_t idx = payload_window(p, b, st.bit_pos);
+        const uint64_t idx = payload_window(p, b, st.bit_pos, sq.P);
         int64_t c = pre;
         for_chunk(min(i1, kp), [&](int i, int64_t q) {
             c += q;
@@ -721,7 +728,7 @@ __device__ __forceinline__ void wide_cdf_stream(const StepParams& p, const WideS
         }
         return;
     }
-    wide_finish<DECODE>(p, b, st, k, kp, sel, exact, S_used, cum_at[1], cum_at[2], shift, sel_key, m, rs, kl,
+    wide_finish<DECODE>(p, sq.P, b, st, k, kp, sel, exact, S_used, cum_at[1], cum_at[2], shift, sel_key, m, rs, kl,
                         want_stats);
 }
 
@@ -787,9 +794,9 @@ __device__ __forceinline__ int wave_min_int(int v) {
 // The exact row sum (forced, unusable bound, or an ambiguous cutoff: ~1 % of stream-steps) is computed here by
 // the block, not handed to the list kernel.
 template <typename T, bool DECODE, typename KeyAt>
-__device__ __forceinline__ void fast_tail(const StepParams& p, const WideStat& w, const int b, const int n,
-                                          const KeyAt kin, uint64_t* keys_out, const int cap, unsigned int* todo,
-                                          uint64_t* s_keys, uint64_t* s_aux) {
+__device__ __forceinline__ void fast_tail(const StepParams& p, const RowQuality& sq, const WideStat& w, const int b,
+                                          const int n, const KeyAt kin, uint64_t* keys_out, const int cap,
+                                          unsigned int* todo, uint64_t* s_keys, uint64_t* s_aux) {
     uint32_t* s_cnt = (uint32_t*)s_aux;
     const int tid = (int)threadIdx.x, lane = tid & (WAVE - 1), wv = tid / WAVE;
     // ---- load (unsorted, as collected) + key range; every key is in registers before the first LDS write
@@ -951,11 +958,11 @@ __device__ __forceinline__ void fast_tail(const StepParams& p, const WideStat& w
     const bool want_stats = !DECODE && p.stats != nullptr;
     RowStats rs{0.0, 0.0, 0.0};
     if ((!DECODE && p.sample) ||
-        (want_stats && !row_stats_from_stream(w.S_r, w.B_r, w.U_r, w.r, m, p.inv_temp, rs))) {
+        (want_stats && !row_stats_from_stream(w.S_r, w.B_r, w.U_r, w.r, m, sq.inv_temp, rs))) {
         defer();
         return;
     }
-    const int Kc = min(n, p.K);
+    const int Kc = min(n, sq.K);
     const uint64_t R = st.hi - st.lo;
     const double Rd = (double)R;
     const double thr = 1.0 / Rd;
@@ -971,7 +978,7 @@ __device__ __forceinline__ void fast_tail(const StepParams& p, const WideStat& w
         for (int r = 0; r < FAST_R; ++r) {
             const int i = r * FAST_THREADS + tid;
             if (i < Kc) {
-                const double e = exp_canon(((double)wkey_val(ks[r]) - m) * p.inv_temp);
+                const double e = exp_canon(((double)wkey_val(ks[r]) - m) * sq.inv_temp);
                 s_e[i] = e;
                 const bool below = e * inv_lo < thr;
                 const bool above = e * inv_hi >= thr;
@@ -997,7 +1004,8 @@ __device__ __forceinline__ void fast_tail(const StepParams& p, const WideStat& w
         // the canonical exact row sum by this block (s_keys is scratch: e_i are recomputed from the registers)
         __syncthreads();
         const char* rowc = (const char*)p.logits + (int64_t)b * p.ld * (int64_t)sizeof(T);
-        const double S = block_exact_row_sum<T, FAST_THREADS, 4096>(p, rowc, m, (double*)s_keys, (double*)(s_aux + 512));
+        const double S = block_exact_row_sum<T, FAST_THREADS, 4096>(p, rowc, m, sq.inv_temp, (double*)s_keys,
+                                                                    (double*)(s_aux + 512));
         exact = true;
         S_used = S;
         fb = Kc;
@@ -1005,7 +1013,7 @@ __device__ __forceinline__ void fast_tail(const StepParams& p, const WideStat& w
         for (int r = 0; r < FAST_R; ++r) {
             const int i = r * FAST_THREADS + tid;
             if (i < Kc) {
-                const double e = exp_canon(((double)wkey_val(ks[r]) - m) * p.inv_temp);
+                const double e = exp_canon(((double)wkey_val(ks[r]) - m) * sq.inv_temp);
                 s_e[i] = e;
                 if (e / S < thr) fb = min(fb, i);
             }
@@ -1019,7 +1027,7 @@ __device__ __forceinline__ void fast_tail(const StepParams& p, const WideStat& w
     }
     NSG_STAMP(p, b, tid, 6);
     int k = fb < 2 ? 2 : fb;
-    if (k > p.topk) k = p.topk;
+    if (k > sq.topk) k = sq.topk;
     // a degenerate row (fewer than two keys): wide_cdf_kernel.  An ambiguous cutoff (fa < fb) was settled by the
     // exact row sum above.
     if (k > Kc) {
@@ -1093,7 +1101,7 @@ __device__ __forceinline__ void fast_tail(const StepParams& p, const WideStat& w
     // ---- selection
     int sel = 0x7FFFFFFF;
     if (!DECODE) {
-        const uint64_t idx = payload_window(p, b, st.bit_pos);
+        const uint64_t idx = payload_window(p, b, st.bit_pos, sq.P);
 #pragma unroll
         for (int r = 0; r < FAST_R; ++r) {
             const int i = r * FAST_THREADS + tid;
@@ -1149,7 +1157,7 @@ __device__ __forceinline__ void fast_tail(const StepParams& p, const WideStat& w
         kl = 0.0;
         for (int i = 0; i < FAST_WAVES; ++i) kl += s_d[8 + i];
     }
-    wide_finish<DECODE>(p, b, st, k, kp, sel, exact, S_used, s_c[1], s_c[2], shift, (uint64_t)s_c[3], m, rs, kl,
+    wide_finish<DECODE>(p, sq.P, b, st, k, kp, sel, exact, S_used, s_c[1], s_c[2], shift, (uint64_t)s_c[3], m, rs, kl,
                         want_stats);
     NSG_STAMP(p, b, tid, 8);
     NSG_STAMP_RT(p, b, tid, 10);
@@ -1276,7 +1284,8 @@ __global__ __launch_bounds__(FAST_THREADS, NSG_FAST_WAVES_PER_SIMD) void wide_on
     int* s_n = (int*)(s_aux + 48);
     float* s_xt = (float*)(s_aux + 52);
     const bool stats = p.stats != nullptr;
-    const double temp = 1.0 / p.inv_temp;
+    const RowQuality sq = row_quality(p, b);  // this stream's table row, or the call's scalars
+    const double temp = 1.0 / sq.inv_temp;
     const float tempf = (float)temp;
     const double Rd = (double)(st.hi - st.lo);
     const float lnthr = (float)(-log(Rd));  // ln(1/R)
@@ -1326,7 +1335,7 @@ __global__ __launch_bounds__(FAST_THREADS, NSG_FAST_WAVES_PER_SIMD) void wide_on
     // (t finite, e = 0, e*t = 0); a real -inf logit makes B_t NaN, i.e. the bound unusable (exact row sum).
     auto sum_tile = [&](const float (&x)[W]) __attribute__((always_inline)) {
         typedef float f2 __attribute__((ext_vector_type(2)));
-        const f2 c2 = {p.c32, p.c32}, n2 = {nrc, nrc};
+        const f2 c2 = {sq.c32, sq.c32}, n2 = {nrc, nrc};
         f2 a2 = {0.0f, 0.0f}, b2 = {0.0f, 0.0f};
 #pragma unroll
         for (int q = 0; q < W; q += 2) {
@@ -1346,7 +1355,7 @@ __global__ __launch_bounds__(FAST_THREADS, NSG_FAST_WAVES_PER_SIMD) void wide_on
 #pragma unroll
             for (int q = 0; q < W; ++q) {
                 const float dx = fmaxf(x[q] - r, -3.0e38f);
-                const float e = __builtin_amdgcn_exp2f(dx * p.c32);
+                const float e = __builtin_amdgcn_exp2f(dx * sq.c32);
                 bb += e * dx;
                 uu += __builtin_amdgcn_exp2f(dx * L2E_F);
             }
@@ -1432,7 +1441,7 @@ __global__ __launch_bounds__(FAST_THREADS, NSG_FAST_WAVES_PER_SIMD) void wide_on
     for (int i = 1; i < FAST_WAVES; ++i) r = fmaxf(r, s_m1[i]);
     if (!(r > -1.0e29f)) r = 0.0f;  // no valid id in the sample
     r = uni_f32(r);
-    nrc = uni_f32(-(r * p.c32));
+    nrc = uni_f32(-(r * sq.c32));
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < NSW; ++i)
@@ -1520,7 +1529,7 @@ __global__ __launch_bounds__(FAST_THREADS, NSG_FAST_WAVES_PER_SIMD) void wide_on
     WideStat w;
     {
         double Sf = 0.0, S_lo = 0.0, S_hi = 0.0;
-        const bool ok = fast_sum_interval_dd(uni_f64(S_r), uni_f64(T_r), r, (double)(bm1 + 0.0f), p.c32, p.inv_temp,
+        const bool ok = fast_sum_interval_dd(uni_f64(S_r), uni_f64(T_r), r, (double)(bm1 + 0.0f), sq.c32, sq.inv_temp,
                                              W, Sf, S_lo, S_hi);
         w.m = uni_f32(bm1);
         w.m2 = -__builtin_inff();  // not tracked (k >= 2 is checked below)
@@ -1674,7 +1683,7 @@ __global__ __launch_bounds__(FAST_THREADS, NSG_FAST_WAVES_PER_SIMD) void wide_on
         key = i < n ? kout[i] : 0ull;
         return i < n;
     };
-    fast_tail<T, DECODE>(p, w, b, n, at, keys_out, cap, todo, s_keys, s_aux);
+    fast_tail<T, DECODE>(p, sq, w, b, n, at, keys_out, cap, todo, s_keys, s_aux);
 }
 
 // ------------------------------------------------------------------------------------------ rank coder

@@ -128,6 +128,9 @@ class HipArithmeticLM:
     slot_compaction = True  # native slot loops: compact the live slots once the queue is drained (off: tests that
                             # read per-step logits by row)
     share_contexts = True  # ``contexts=``: messages with equal contexts share the context's KV pages (off: A/B, tests)
+    # ``qualities=``: messages whose top-k is beyond the single-pass limit run as one mixed batch on the wide kernels
+    # (off: one call per distinct such quality -- A/B, tests)
+    mix_wide_qualities = True
     # ``contexts=``: different contexts share the pages of a common prefix, in 64-token blocks (native
     # path, fp16 pages and share_contexts on -- with an fp8 cache the call behaves as without it)
     share_prefixes = True
@@ -303,9 +306,11 @@ class HipArithmeticLM:
         then reads every stream's values from its row of a device table (``ns_set_stream_quality``), so the messages
         still run as ONE batch; message ``m``'s tokens equal ``encode_batch([bits], ..., quality=qualities[m])[0]``.
         ``finish_sent`` is a flag of the whole step and must agree across the call.  All-equal ``qualities`` take the
-        ``quality`` path.  Messages whose top-k exceeds the single-pass limit (``ns_max_topk``: the wide path takes
-        one quality per call) run as one more call per distinct such quality, results back in the caller's order
-        (``last_schedule["quality_groups"]``).
+        ``quality`` path.  Messages whose top-k exceeds the single-pass limit (``ns_max_topk``; the api default,
+        top-k 50,000, is one) run as ONE more mixed batch on the wide kernels (``ns_set_stream_quality_wide``), so a
+        call has at most two groups -- at or below the limit, and beyond it -- with the results back in the caller's
+        order (``last_schedule["quality_groups"]``).  With ``mix_wide_qualities = False`` every distinct quality
+        beyond the limit runs as a call of its own instead (the same tokens).
 
         With ``graphs`` (default) the native model's per-token step is captured once as a hipGraph and replayed,
         which removes the per-launch host cost (it dominates at small batch, and at B = 4096 it keeps the GPU busy
@@ -323,7 +328,8 @@ class HipArithmeticLM:
             return []
         kw = dict(check_every=check_every, stall_steps=stall_steps, return_stats=return_stats, stop_text=stop_text,
                   graphs=graphs, slots=slots)
-        groups = _quality_groups(plist, self._single_pass_limit()) if plist is not None else None
+        groups = _quality_groups(plist, self._single_pass_limit(), self.mix_wide_qualities) \
+            if plist is not None else None
         if groups is not None and len(groups) > 1:
             n_enc, n_dec = len(self._encode_states), len(self._decode_states)
             res = self._by_group(self.encode_batch, bit_lists, groups, context, contexts, qualities, return_stats, **kw)
@@ -436,8 +442,9 @@ class HipArithmeticLM:
         a message's pages mapped when it is admitted); with ``graphs`` the per-token step (coder + GPT-2 decode) is a
         replayed hipGraph, as in :meth:`encode_batch`.  Non-native models ignore ``graphs`` (eager lockstep loop).
         ``context`` / ``contexts`` as in :meth:`encode_batch`: one shared context, or one per token list; ``quality``
-        / ``qualities`` likewise (one mixed batch, top-k beyond the single-pass limit grouped,
-        ``last_decode_schedule["quality_groups"]``).
+        / ``qualities`` likewise (one mixed batch at or below the single-pass limit and one beyond it,
+        ``last_decode_schedule["quality_groups"]``; ``mix_wide_qualities = False``: one call per distinct quality
+        beyond the limit).
         ``chunk`` = C in 2..16 (native model, no attention window; default 1 = one token per step): every cover token
         is known before the first step, so a slot's next C tokens go through the LM in ONE forward
         (``SlotDecoder.run_chunk``; its K/V pages are read once per C tokens) and only the coder runs token by token --
@@ -454,7 +461,8 @@ class HipArithmeticLM:
         quality, plist = self._quality_or_many(quality, qualities, B)
         if B == 0:
             return []
-        groups = _quality_groups(plist, self._single_pass_limit()) if plist is not None else None
+        groups = _quality_groups(plist, self._single_pass_limit(), self.mix_wide_qualities) \
+            if plist is not None else None
         if groups is not None and len(groups) > 1:
             res = self._by_group(self.decode_batch, token_lists, groups, context, contexts, qualities, False,
                                  graphs=graphs, slots=slots, chunk=chunk)
@@ -778,11 +786,16 @@ class HipArithmeticLM:
         return sess.tokens(), (sess.stats() if stats else None)
 
 
-def _quality_groups(plist: Sequence[CoderParams], limit: int) -> List[List[int]]:
+def _quality_groups(plist: Sequence[CoderParams], limit: int, mix_wide: bool = False) -> List[List[int]]:
     """Message indices per call of a ``qualities=`` request: every message whose top-k fits the single-pass kernel
-    (``limit`` = ``ns_max_topk``) in ONE mixed group, then one group per distinct (temp, topk, precision) beyond it
-    (the wide path takes one quality per call), in order of first appearance."""
+    (``limit`` = ``ns_max_topk``) in ONE mixed group, then the messages beyond it -- with ``mix_wide`` as ONE more
+    mixed group (the wide kernels read per-stream rows, ``ns_set_stream_quality_wide``), else one group per distinct
+    (temp, topk, precision), in order of first appearance.  The two mixed groups stay apart: the single-pass step is
+    several times faster than the wide chain, which would otherwise serve the narrow messages too."""
     mixed = [i for i, p in enumerate(plist) if p.topk <= limit]
+    if mix_wide:
+        beyond = [i for i, p in enumerate(plist) if p.topk > limit]
+        return ([mixed] if mixed else []) + ([beyond] if beyond else [])
     wide: Dict[tuple, List[int]] = {}
     for i, p in enumerate(plist):
         if p.topk > limit:

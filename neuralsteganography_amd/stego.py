@@ -216,7 +216,8 @@ def stego_encode_batch(messages: Sequence[bytes], *, chunk_bytes: int = 256, use
     """Every message -> its :class:`EncodeResult`; all packets of all messages are encoded as one batch.
     ``qualities`` (one per message, as each ``stego_encode`` call of the reference has its own ``quality``): every
     packet of message ``i`` is encoded with ``qualities[i]`` merged over :data:`DEFAULT_QUALITY`; ``quality`` is then
-    not given.
+    not given.  On the HIP provider the packets still run as one batch when the qualities differ -- the api default
+    (top-k 50,000) included: at most one batch at or below the single-pass top-k limit and one beyond it.
     ``seed_texts`` (one per message, as each ``stego_encode`` call of the reference has its own ``seed_text``):
     every packet of message ``i`` is encoded with ``encode_seed(seed_texts[i])``; ``seed_text`` is then unused."""
     per_msg = _seed_contexts(lm, seed_texts, len(messages)) if seed_texts is not None else None
@@ -289,9 +290,10 @@ def stego_decode_batch(span_sets: Sequence[Iterable[List[int]]], *, use_crc: boo
     """Every message's spans -> its bytes, all spans decoded as one batch.  Errors (missing chunks, CRC, RS,
     cfg mismatch) raise for the first failing message, or are returned in its slot with
     ``return_errors=True``.  ``seed_texts``: one seed text per message, ``qualities``: one quality per message, as
-    in :func:`stego_encode_batch`.  ``chunk`` (1..16, default 1): known cover tokens per LM forward, passed to the
-    provider's ``decode_batch`` (the same bits, fewer passes over the KV pages); ``ValueError`` outside 1..16 or
-    with a provider that has no chunked decode."""
+    in :func:`stego_encode_batch` (one batch, or two when top-k values lie on both sides of the single-pass limit).
+    ``chunk`` (1..16, default 1): known cover tokens per LM forward, passed to the provider's ``decode_batch`` (the
+    same bits, fewer passes over the KV pages); ``ValueError`` outside 1..16 or with a provider that has no chunked
+    decode."""
     span_sets = list(span_sets)
     per_msg = _seed_contexts(lm, seed_texts, len(span_sets)) if seed_texts is not None else None
     mode = normalise_ecc(ecc)
