@@ -279,6 +279,35 @@ int ns_set_stream_quality(ns_ctx* ctx, const ns_stream_quality* d_table, int k_m
  * registered. */
 int ns_set_stream_quality_wide(ns_ctx* ctx, const ns_stream_quality* d_table, int k_max);
 
+/* Per-stream draw row of the sampler: what keys a stream's draws and where the stream ends.  One row per stream in
+ * DEVICE memory, written by the caller (no kernel writes the table).  The layout is fixed: 32 bytes, fields at the
+ * offsets below. */
+typedef struct ns_sample_draw {
+    uint64_t seed;       /*  0: seed of the stream's draws                                  */
+    int64_t gid;         /*  8: draw id of the stream (what stream_offset + b is without rows) */
+    int32_t length;      /* 16: tokens the stream samples; parked once ntokens >= length    */
+    int32_t reserved[3]; /* 20: 0                                                           */
+} ns_sample_draw;
+#define NS_SAMPLE_DRAW_BYTES 32
+
+/* The sampler step with every per-stream value taken from DEVICE tables given to the call itself (the registered
+ * table of ns_set_stream_quality is not used): d_quality[b] is stream b's ns_stream_quality row, filled by
+ * ns_stream_quality_fill for this k_max (the sampler ignores `precision`; the host maps "every id" to topk = vocab),
+ * d_draws[b] its ns_sample_draw row.  Token t of stream b is drawn with splitmix64(row.seed, row.gid, t) -- nothing
+ * depends on the row index b, so a stream keeps its draws in whatever row it runs -- and the integers emitted are
+ * those ns_sample_step emits for the same (temp, topk, seed, gid).  A stream with ntokens >= row.length is PARKED: the
+ * step writes nothing for it (state, history, statistics and trace stay as they are, d_out_token[b] keeps its last
+ * value), so a loop may run further steps without a host check.  Every host decision -- single-pass or wide, the
+ * rank-slot bucket, the split or wave-per-stream form, the sample -- follows k_max alone, so a captured step stays
+ * valid whatever the rows hold; a row's K may be anything in [1, k_max].  The other arguments are those of
+ * ns_sample_step.  NS_ERR_CONFIG for a null or misaligned (8 bytes) table, k_max < 1, a NS_DTYPE_F64 context, a
+ * registered quality table (as ns_sample_step), and min(k_max, valid ids) > ns_max_topk(dtype) on a context created
+ * without the wide-path buffers. */
+int ns_sample_step_streams(ns_ctx* ctx, const void* d_logits, int64_t ld, int B, const ns_stream_quality* d_quality,
+                           const ns_sample_draw* d_draws, int k_max, ns_stream_state* d_state, int32_t* d_out_token,
+                           int32_t* d_token_hist, int64_t hist_stride, const int32_t* banned, int nbanned,
+                           double* d_stats, ns_step_trace* d_trace, uint32_t step_flags, void* hip_stream);
+
 /* Rare-event diagnostics, cumulative since ns_create: counters[0] = stream-steps that took the exact-sum
  * path, counters[1] = candidate-buffer overflow compactions, counters[2] = speculative-threshold misses
  * (row re-read), counters[3] = top-K selections that left the histogram fast path (value ties or a skewed

@@ -27,7 +27,8 @@ NS_MAX_BANNED = 8
 
 EXPORTS = ("ns_create", "ns_destroy", "ns_last_error", "ns_version", "ns_max_topk", "ns_set_split_max_batch",
            "ns_init_state",
-           "ns_encode_step", "ns_decode_step", "ns_set_sentence_end", "ns_set_stats", "ns_sample_step", "ns_set_rank_export",
+           "ns_encode_step", "ns_decode_step", "ns_set_sentence_end", "ns_set_stats", "ns_sample_step", "ns_sample_step_streams",
+           "ns_set_rank_export",
            "ns_rank_encode_step", "ns_set_rank_rows", "ns_rank_decode_step", "ns_token_probs",
            "ns_stream_quality_fill", "ns_set_stream_quality", "ns_set_stream_quality_wide",
            "ns_read_counters", "ns_decode_attention", "ns_decode_attention_dev", "ns_decode_attention_prefix",
@@ -81,6 +82,17 @@ class NsStreamQuality(ctypes.Structure):
 
 NS_STREAM_QUALITY_BYTES = 32
 assert ctypes.sizeof(NsStreamQuality) == NS_STREAM_QUALITY_BYTES
+
+
+class NsSampleDraw(ctypes.Structure):
+    """``ns_sample_draw`` (include/nsg_coder.h): what keys one sampler stream's draws, and its length."""
+
+    _fields_ = [("seed", ctypes.c_uint64), ("gid", ctypes.c_int64), ("length", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 3)]
+
+
+NS_SAMPLE_DRAW_BYTES = 32
+assert ctypes.sizeof(NsSampleDraw) == NS_SAMPLE_DRAW_BYTES
 
 
 def lib() -> ctypes.CDLL:
@@ -143,6 +155,9 @@ def lib() -> ctypes.CDLL:
     L.ns_sample_step.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_uint64, ctypes.c_int64, vp, vp,
                                  vp, ctypes.c_int64, ctypes.c_double, ctypes.c_int, i32p, ctypes.c_int, vp, vp,
                                  ctypes.c_uint32, vp]
+    L.ns_sample_step_streams.restype = ctypes.c_int
+    L.ns_sample_step_streams.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int, vp, vp, ctypes.c_int, vp, vp, vp,
+                                         ctypes.c_int64, i32p, ctypes.c_int, vp, vp, ctypes.c_uint32, vp]
     L.ns_read_counters.restype = ctypes.c_int
     L.ns_read_counters.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.ns_score_rows.restype = ctypes.c_int

@@ -95,14 +95,30 @@ def decode_arithmetic(model, enc, text: str, context: Sequence[int], device: str
                                    topk=topk)[0]
 
 
-def sample_batch(model, enc, length: int, context: Sequence[int], n: int, temperature: float = 1.0,
-                 device: str = "cuda", topk: int = -1, seed: int = 0
-                 ) -> List[Tuple[List[int], float, float, float]]:
-    """n independent samples -> per sample ``(tokens, avg_NLL, avg_KL, avg_Hq)``."""
+def sample_batch(model, enc, length: int, context: Optional[Sequence[int]], n: int, temperature: float = 1.0,
+                 device: str = "cuda", topk: int = -1, seed: int = 0, *,
+                 contexts: Optional[Sequence[Sequence[int]]] = None, lengths: Optional[Sequence[int]] = None,
+                 temperatures: Optional[Sequence[float]] = None, topks: Optional[Sequence[int]] = None,
+                 seeds: Optional[Sequence[int]] = None) -> List[Tuple[List[int], float, float, float]]:
+    """n independent samples -> per sample ``(tokens, avg_NLL, avg_KL, avg_Hq)``.
+
+    ``contexts``, ``lengths``, ``temperatures``, ``topks``, ``seeds`` (one entry per sample each; ``context`` is
+    None with ``contexts``, and ``n == len(contexts)``) make the samples the messages of ONE slot-scheduled batch:
+    sample i is ``sample(model, enc, lengths[i], contexts[i], temperatures[i], topk=topks[i], seed=seeds[i])``."""
     _ = device
+    lm = _provider(model, enc)
+    if any(v is not None for v in (contexts, lengths, temperatures, topks, seeds)):
+        if contexts is not None and len(contexts) != int(n):
+            raise ValueError(f"{len(contexts)} contexts for n = {n}")
+        if lengths is None and length <= 0:
+            raise ValueError("length must be positive")  # sample.py:7 asserts length > 0
+        toks, stats = lm.sample_batch(
+            int(n), length, list(context)[-1022:] if context is not None else None,
+            contexts=[list(c)[-1022:] for c in contexts] if contexts is not None else None, lengths=lengths,
+            temperatures=temperatures, topks=topks, seeds=seeds, temperature=temperature, topk=topk, seed=seed)
+        return [(t, s["avg_NLL"], s["avg_KL"], s["avg_Hq"]) for t, s in zip(toks, stats)]
     if length <= 0:
         raise ValueError("length must be positive")  # sample.py:7 asserts length > 0
-    lm = _provider(model, enc)
     toks, stats = lm.sample_batch(int(n), int(length), list(context)[-1022:], temperature=temperature, topk=topk,
                                   seed=seed)
     return [(t, s["avg_NLL"], s["avg_KL"], s["avg_Hq"]) for t, s in zip(toks, stats)]

@@ -684,16 +684,40 @@ def decode_batch(ctx: CoderContext, token_lists: Sequence[Sequence[int]], logits
     return sess.bits()
 
 
+def sample_draw_rows(seeds: Sequence[int], gids: Sequence[int], lengths: Sequence[int]) -> np.ndarray:
+    """``ns_sample_draw`` rows as [n, 4] int64 (the 32-byte rows as the device table holds them): seed (taken
+    modulo 2^64), draw id, length (int32, the reserved words after it zero)."""
+    n = len(seeds)
+    if len(gids) != n or len(lengths) != n:
+        raise ConfigurationError("one seed, one draw id and one length per stream")
+    if any(int(v) < 0 or int(v) >= 1 << 31 for v in lengths):
+        raise ConfigurationError("a stream's length must be within [0, 2^31)")
+    rows = np.zeros((n, 4), dtype=np.int64)
+    rows[:, 0] = np.asarray([int(s) & ((1 << 64) - 1) for s in seeds], dtype=np.uint64).view(np.int64)
+    rows[:, 1] = np.asarray([int(g) for g in gids], dtype=np.int64)
+    rows[:, 2] = np.asarray([int(v) for v in lengths], dtype=np.int64)
+    return rows
+
+
 class SampleSession:
     """B independent non-stego sampling streams (``code_base/sample.py:22-48``), one HIP launch per token.
 
     Draws are counter based (``ns_sample_step``): token t of stream b uses splitmix64(seed, stream_offset + b,
     t), so a run is reproducible and shardable (a rank passes its first global stream id as
     ``stream_offset``).  ``topk <= 0`` samples from every id.  Statistics (avg_NLL, avg_KL, avg_Hq of
-    ``sample()``) are accumulated on the device when ``stats=True``."""
+    ``sample()``) are accumulated on the device when ``stats=True``.
 
-    def __init__(self, ctx: CoderContext, B: int, *, seed: int, topk: int, temp: float, stream_offset: int = 0,
-                 max_tokens: int = 1024, stats: bool = True):
+    With ``quality`` (one :class:`StreamQuality` row per stream; its precision is not used) and ``seeds``, ``gids``,
+    ``lengths`` (one each per stream) the session runs ``ns_sample_step_streams`` instead: stream b has its own
+    temperature and top-k, draws token t with splitmix64(seeds[b], gids[b], t) whatever row it is in, and is parked
+    -- nothing of it written -- once it has ``lengths[b]`` tokens.  ``seed``, ``topk``, ``temp`` and
+    ``stream_offset`` are then not used.  Such a session also has the slot operations of :class:`EncodeSession`
+    (:meth:`load_slots`, :meth:`park_slots`, :meth:`compact`, :meth:`harvest`)."""
+
+    def __init__(self, ctx: CoderContext, B: int, *, seed: int = 0, topk: int = -1, temp: float = 1.0,
+                 stream_offset: int = 0, max_tokens: int = 1024, stats: bool = True,
+                 quality: Optional[StreamQuality] = None, seeds: Optional[Sequence[int]] = None,
+                 gids: Optional[Sequence[int]] = None, lengths: Optional[Sequence[int]] = None):
         torch = _torch()
         if B < 1 or B > ctx.max_batch:
             raise ConfigurationError(f"batch {B} outside [1, {ctx.max_batch}]")
@@ -703,8 +727,23 @@ class SampleSession:
         self.seed = int(seed) & ((1 << 64) - 1)
         self.topk, self.temp, self.stream_offset = int(topk), float(temp), int(stream_offset)
         dev = torch.device("cuda", ctx.device)
-        self.state = _state_tensor(self.B, dev)
-        ctx.check(_lib.lib().ns_init_state(ctx._h, _ptr(self.state), self.B, _stream_handle()), "ns_init_state")
+        self.qtable = self.draws = None
+        self.k_max = 0
+        if quality is not None:
+            if seeds is None or gids is None or lengths is None:
+                raise ConfigurationError("per-stream quality rows go with per-stream seeds, gids and lengths")
+            _check_quality(ctx, self.B, quality)
+            rows = sample_draw_rows(seeds, gids, lengths)
+            if rows.shape[0] != self.B:
+                raise ConfigurationError(f"{rows.shape[0]} draw rows for {self.B} streams")
+            self.qtable, self.k_max = quality.table(dev), quality.k_max
+            self.draws = torch.from_numpy(rows).to(dev)
+            self.state = quality.init_rows(dev)
+        elif seeds is not None or gids is not None or lengths is not None:
+            raise ConfigurationError("per-stream seeds, gids and lengths go with per-stream quality rows")
+        else:
+            self.state = _state_tensor(self.B, dev)
+            ctx.check(_lib.lib().ns_init_state(ctx._h, _ptr(self.state), self.B, _stream_handle()), "ns_init_state")
         self.out_token = torch.zeros(self.B, dtype=torch.int32, device=dev)
         self.hist = torch.full((self.B, int(max_tokens)), -1, dtype=torch.int32, device=dev)
         self.stats_acc = torch.zeros((self.B, 4), dtype=torch.float64, device=dev) if stats else None
@@ -718,6 +757,15 @@ class SampleSession:
 
     def step(self, logits, *, diag_flags: int = 0):
         _check_logits(self.ctx, self.B, logits)
+        if self.draws is not None:  # a stream ends at its own length (at most the history's width: load_slots)
+            rc = _lib.lib().ns_sample_step_streams(
+                self.ctx._h, _ptr(logits), logits.stride(0), self.B, _ptr(self.qtable), _ptr(self.draws),
+                int(self.k_max), _ptr(self.state), _ptr(self.out_token), _ptr(self.hist), self.hist.shape[1],
+                self.ctx._banned, self.ctx._nbanned, _ptr(self.stats_acc), _ptr(self.trace), int(diag_flags),
+                _stream_handle())
+            self.ctx.check(rc, "ns_sample_step_streams")
+            self.steps += 1
+            return self.out_token
         if self.steps >= self.hist.shape[1]:
             raise ConfigurationError("token history full: raise max_tokens")
         rc = _lib.lib().ns_sample_step(
@@ -734,8 +782,73 @@ class SampleSession:
         return np.rec.fromarrays([t[:, 0], t[:, 1], t[:, 2], t[:, 3], t[:, 4]], names="k,kprime,sel,n,token")
 
     def tokens(self) -> List[List[int]]:
+        if self.draws is not None:  # every stream's own count (at most its length)
+            nt = _state_fields(self.state)["ntokens"]
+            return _rows_to_lists(self.hist, np.minimum(nt, self.hist.shape[1]))
         n = min(self.steps, self.hist.shape[1])
         return _rows_to_lists(self.hist, np.full(self.B, n))
+
+    # ---------------------------------------------------------------- slots (lm/slots.py: refill, compaction)
+    def _tables(self) -> None:
+        if self.draws is None:
+            raise ConfigurationError("slot operations need a session created with per-stream tables")
+
+    def load_slots(self, slots: Sequence[int], quality: StreamQuality, seeds: Sequence[int], gids: Sequence[int],
+                   lengths: Sequence[int]) -> None:
+        """Start new streams in ``slots`` (rows of this session): their quality and draw rows, a fresh state
+        (``ntokens`` 0) and, with stats, zeroed accumulators.  The token history row is reused from position 0, and
+        the history is widened first when an admitted length does not fit it."""
+        self._tables()
+        torch = _torch()
+        n = len(slots)
+        if n == 0:
+            return
+        if len(quality) != n or quality.k_max != self.k_max:
+            raise ConfigurationError("load_slots: one quality row per slot, filled for the session's k_max")
+        rows = sample_draw_rows(seeds, gids, lengths)
+        if rows.shape[0] != n:
+            raise ConfigurationError("load_slots: one draw row per slot")
+        dev = self.state.device
+        need = int(rows[:, 2].max())
+        if need > self.hist.shape[1]:
+            new = torch.full((self.B, need), -1, dtype=torch.int32, device=dev)
+            new[:, : self.hist.shape[1]] = self.hist
+            self.hist = new
+        idx = torch.as_tensor(np.asarray(slots, dtype=np.int64), device=dev)
+        self.qtable[idx] = quality.table(dev)
+        self.draws[idx] = torch.from_numpy(rows).to(dev)
+        self.state[idx] = quality.init_rows(dev)
+        if self.stats_acc is not None:
+            self.stats_acc[idx] = 0
+
+    def park_slots(self, slots: Sequence[int]) -> None:
+        """Park ``slots`` (length 0 in their draw rows): the step writes nothing for them."""
+        self._tables()
+        if len(slots) == 0:
+            return
+        torch = _torch()
+        idx = torch.as_tensor(np.asarray(slots, dtype=np.int64), device=self.state.device)
+        self.draws[idx, 2] = 0
+
+    def compact(self, keep: Sequence[int]) -> None:
+        """Keep rows ``keep`` (in that order) of every per-stream buffer: the session now has len(keep) streams."""
+        self._tables()
+        torch = _torch()
+        idx = torch.as_tensor(np.asarray(keep, dtype=np.int64), device=self.state.device)
+        for name in ("state", "out_token", "hist", "stats_acc", "trace", "qtable", "draws"):
+            t = getattr(self, name)
+            if t is not None:
+                setattr(self, name, t.index_select(0, idx).contiguous())
+        self.B = len(keep)
+
+    def harvest(self, slots: Sequence[int], lengths: Sequence[int]):
+        """``(token lists, [n, 4] accumulators or None)`` of ``slots``, whose streams have reached ``lengths``."""
+        self._tables()
+        torch = _torch()
+        idx = torch.as_tensor(np.asarray(slots, dtype=np.int64), device=self.state.device)
+        toks = _rows_to_lists(self.hist.index_select(0, idx), lengths)
+        acc = self.stats_acc.index_select(0, idx).cpu().numpy() if self.stats_acc is not None else None
+        return toks, acc
 
     def stats(self) -> List[dict]:
         if self.stats_acc is None:

@@ -663,7 +663,7 @@ __device__ __forceinline__ void mask_tile(const StepParams& p, float (&x)[W], in
 template <int NSK>
 __device__ __forceinline__ void sample_tail(const StepParams& p, int b, const ns_stream_state& st,
                                             const uint64_t (&sk)[NSK], const double (&e)[NSK], int nsk, int K,
-                                            double m, const RowStats& rs, int lane, bool stats) {
+                                            double m, const RowStats& rs, int lane, bool stats, double inv_temp) {
     int ks = K;
 #pragma unroll
     for (int s = 0; s < NSK; ++s) {
@@ -689,7 +689,8 @@ __device__ __forceinline__ void sample_tail(const StepParams& p, int b, const ns
         if (s < nsk) carry = (int64_t)readlane64((uint64_t)c, WAVE - 1);
     }
     const uint64_t total = (uint64_t)carry;
-    const uint64_t u = rand64(p.seed, p.stream_offset + b, st.ntokens);
+    const DrawKey dk = draw_key(p, b);  // this stream's draw row, or the call's (seed, stream_offset + b)
+    const uint64_t u = rand64(dk.seed, dk.gid, st.ntokens);
     const uint64_t idx = __umul64hi(u, total);
     int sel = -1;
 #pragma unroll
@@ -712,7 +713,7 @@ __device__ __forceinline__ void sample_tail(const StepParams& p, int b, const ns
         for (int s = 0; s < NSK; ++s) {
             if (s < nsk && s * WAVE + lane < ks) {
                 const double xi = (double)key_val(sk[s]) - m;
-                const double lq = xi * p.inv_temp - logE;
+                const double lq = xi * inv_temp - logE;
                 const double q = e[s] / E;
                 kl += q * (lq - (xi - rs.lse1));
                 h += q * lq;
@@ -783,6 +784,7 @@ __global__ __launch_bounds__((NSPLIT > 1 ? NSPLIT : WPB) * WAVE, NSG_MIN_WAVES_P
         }
     } else {
         if (p.active && !p.active[b]) return;
+        if (!DECODE && sample_parked(p, b, st.ntokens)) return;  // past its length: nothing is written
     }
 
     const int V = p.V;
@@ -1293,7 +1295,7 @@ __global__ __launch_bounds__((NSPLIT > 1 ? NSPLIT : WPB) * WAVE, NSG_MIN_WAVES_P
             rs = wave_row_stats<T>(p, rowc, m, lane, sq.inv_temp);
     }
     if (!DECODE && p.sample) {
-        sample_tail<NSK>(p, b, st, sk, e, nsk, K, m, rs, lane, want_stats);
+        sample_tail<NSK>(p, b, st, sk, e, nsk, K, m, rs, lane, want_stats, sq.inv_temp);
         return;
     }
     const uint64_t R = st.hi - st.lo;
@@ -1705,7 +1707,7 @@ static bool launch(ns_ctx* ctx, const nsg::StepParams& p, hipStream_t s) {
 
 extern "C" {
 
-const char* ns_version(void) { return "nsgcoder 0.31.3 gfx950"; }
+const char* ns_version(void) { return "nsgcoder 0.31.4 gfx950"; }
 
 int ns_set_split_max_batch(int max_batch) {
     const int prev = split_setting();
@@ -1954,6 +1956,44 @@ int ns_sample_step(ns_ctx* ctx, const void* d_logits, int64_t ld, int B, uint64_
     const bool ok = p.K > ns_max_topk(ctx->dtype) ? nsg_wide_launch(ctx, p, false, (hipStream_t)hip_stream)
                                                   : launch<false>(ctx, p, (hipStream_t)hip_stream);
     if (!ok) return fail(ctx, NS_ERR_HIP, "ns_sample_step: launch failed");
+    return NS_OK;
+}
+
+int ns_sample_step_streams(ns_ctx* ctx, const void* d_logits, int64_t ld, int B, const ns_stream_quality* d_quality,
+                           const ns_sample_draw* d_draws, int k_max, ns_stream_state* d_state, int32_t* d_out_token,
+                           int32_t* d_token_hist, int64_t hist_stride, const int32_t* banned, int nbanned,
+                           double* d_stats, ns_step_trace* d_trace, uint32_t step_flags, void* hip_stream) {
+    if (!ctx) return fail(ctx, NS_ERR_CONFIG, "null context");
+    if (ctx->dtype == NS_DTYPE_F64)
+        return fail(ctx, NS_ERR_CONFIG, "ns_sample_step_streams: a NS_DTYPE_F64 context holds provider probability rows (rank coder only)");
+    if (ctx->quality) return fail(ctx, NS_ERR_CONFIG, "ns_sample_step_streams: a stream quality table is registered");
+    if (!d_quality || !d_draws) return fail(ctx, NS_ERR_CONFIG, "ns_sample_step_streams: null quality or draw table");
+    if (k_max < 1 || (((uintptr_t)d_quality | (uintptr_t)d_draws) & 7u) != 0u)
+        return fail(ctx, NS_ERR_CONFIG, "ns_sample_step_streams: k_max must be positive and the tables 8-byte aligned");
+    {  // the wide chain needs the buffers of a context created for it (the banned ids are known here)
+        int ban[NS_MAX_BANNED];
+        if (nbanned < 0 || nbanned > NS_MAX_BANNED || (nbanned > 0 && !banned))
+            return fail(ctx, NS_ERR_CONFIG, "too many banned ids");
+        const int nvalid = ctx->vocab - clean_banned(ctx->vocab, banned, nbanned, ban);
+        if (std::min(k_max, nvalid) > ns_max_topk(ctx->dtype) && !ctx->wide.keys_in)
+            return fail(ctx, NS_ERR_CONFIG,
+                        "topk beyond the single-pass limit (ns_max_topk): create the context with max_k >= topk");
+    }
+    nsg::StepParams p;
+    // every host decision follows k_max alone (the rows' temperature and topk are read by the kernels)
+    int rc = prepare(ctx, p, d_logits, ld, B, 1.0, k_max, banned, nbanned, d_trace, step_flags, d_state);
+    if (rc != NS_OK) return rc;
+    if (!d_out_token) return fail(ctx, NS_ERR_CONFIG, "ns_sample_step_streams: null output pointer");
+    p.sample = 1;
+    p.quality = d_quality;
+    p.draws = d_draws;
+    p.stats = d_stats;
+    p.out_token = d_out_token;
+    p.hist = d_token_hist;
+    p.hist_stride = d_token_hist ? hist_stride : 0;
+    const bool ok = p.K > ns_max_topk(ctx->dtype) ? nsg_wide_launch(ctx, p, false, (hipStream_t)hip_stream)
+                                                  : launch<false>(ctx, p, (hipStream_t)hip_stream);
+    if (!ok) return fail(ctx, NS_ERR_HIP, "ns_sample_step_streams: launch failed");
     return NS_OK;
 }
 

@@ -320,6 +320,9 @@ struct StepParams {
     // inv_temp, c32 and spec_j above hold for every stream.  With a table, K and spec_j above are those of the call's
     // k_max (host decisions).
     const ns_stream_quality* quality;
+    // per-stream draw rows of the sampler (ns_sample_step_streams), nullable: then seed and stream_offset + b above
+    // key the draw and no stream is parked
+    const ns_sample_draw* draws;
 };
 
 // The quality of stream b (wave-uniform): its table row, or the call's scalars.  b is wave-uniform, so the row is
@@ -381,6 +384,31 @@ __device__ __forceinline__ uint64_t rand64(uint64_t seed, int64_t gid, int64_t t
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
+}
+
+// The draw key and length of sampler stream b (wave-uniform, pinned to scalar registers like row_quality): its draw
+// row, or (seed, stream_offset + b) of the call and no length.  Nothing of a row's draws depends on b.
+struct DrawKey {
+    uint64_t seed;
+    int64_t gid;
+    int length;  // the stream is parked once ntokens >= length
+};
+__device__ __forceinline__ DrawKey draw_key(const StepParams& p, int b) {
+    DrawKey k{p.seed, p.stream_offset + b, 0x7FFFFFFF};
+    if (p.draws) {
+        const ns_sample_draw row = p.draws[b];
+        const uint64_t g = (uint64_t)row.gid;
+        k.seed = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(row.seed >> 32)) << 32) |
+                 __builtin_amdgcn_readfirstlane((uint32_t)row.seed);
+        k.gid = (int64_t)(((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(g >> 32)) << 32) |
+                          __builtin_amdgcn_readfirstlane((uint32_t)g));
+        k.length = __builtin_amdgcn_readfirstlane(row.length);
+    }
+    return k;
+}
+// A sampler stream past its length is parked: the step writes nothing for it (ns_sample_step_streams).
+__device__ __forceinline__ bool sample_parked(const StepParams& p, int b, int ntokens) {
+    return p.draws && ntokens >= __builtin_amdgcn_readfirstlane(p.draws[b].length);
 }
 
 constexpr float L2E_F = 1.44269504088896341f;   // log2(e), fp32 (untempered fast exps of the statistics)

@@ -527,7 +527,8 @@ __device__ __forceinline__ void wide_cdf_stream(const StepParams& p, const WideS
         for (int i = i0; i < i1; ++i) local += q_of(i);
         int64_t total;
         const int64_t pre = block_excl_scan(local, sml, total);
-        const uint64_t u = rand64(p.seed, p.stream_offset + b, st.ntokens);
+        const DrawKey dk = draw_key(p, b);  // this stream's draw row, or the call's (seed, stream_offset + b)
+        const uint64_t u = rand64(dk.seed, dk.gid, st.ntokens);
         const uint64_t idx = __umul64hi(u, (uint64_t)total);
         int sel_l = 0x7FFFFFFF;
         {
@@ -1258,6 +1259,9 @@ __global__ __launch_bounds__(FAST_THREADS, NSG_FAST_WAVES_PER_SIMD) void wide_on
         active = false;
     }
     if (DECODE && p.active && !p.active[b]) active = false;
+    // a sampler stream past its length (ns_sample_step_streams) is parked like a finished encode stream: off the
+    // work list, nothing of it written
+    if (!DECODE && p.sample && sample_parked(p, b, st.ntokens)) active = false;
     if (!active) {
         if (tid == 0) {
             ws[b].active = 0;

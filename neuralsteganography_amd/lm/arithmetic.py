@@ -766,12 +766,39 @@ class HipArithmeticLM:
             logits = self._lm_step(torch.tensor(feed, device=self.device, dtype=torch.long), nxt)
         return sess.bits(), counts, lists, edits
 
-    def sample_batch(self, B: int, length: int, context: Sequence[int], *, temperature: float = 1.0,
-                     topk: int = -1, seed: int = 0, stream_offset: int = 0, stats: bool = True):
+    def sample_batch(self, B: int, length: int, context: Optional[Sequence[int]] = None, *,
+                     contexts: Optional[Sequence[Sequence[int]]] = None, lengths: Optional[Sequence[int]] = None,
+                     temperatures: Optional[Sequence[float]] = None, topks: Optional[Sequence[int]] = None,
+                     seeds: Optional[Sequence[int]] = None, slots: Optional[int] = None,
+                     graphs: Optional[bool] = None, temperature: float = 1.0, topk: int = -1, seed: int = 0,
+                     stream_offset: int = 0, stats: bool = True):
         """B independent non-stego samples of ``length`` tokens from one context (code_base/sample.py, batched):
-        returns ``(token lists, per-stream {avg_NLL, avg_KL, avg_Hq})``."""
+        returns ``(token lists, per-stream {avg_NLL, avg_KL, avg_Hq})``.
+
+        With none of ``contexts``, ``lengths``, ``temperatures``, ``topks``, ``seeds``, ``slots`` and ``graphs`` the
+        B streams run in lockstep from the one ``context`` (``ns_sample_step``), stream b drawing with
+        ``(seed, stream_offset + b)``.
+
+        With any of them the samples are B MESSAGES of one slot-scheduled batch (``lm/slots.py`` ``SlotSampler``,
+        ``ns_sample_step_streams``): message i has its own context (``contexts[i]``, else ``context``), length
+        (``lengths[i]``, else ``length``), temperature and top-k (``temperatures[i]`` / ``topks[i]``, else the
+        scalars; top-k <= 0: every id) and draw key -- ``(seed, stream_offset + i)`` without ``seeds``, which makes
+        the all-scalar call a special case and keeps ``stream_offset`` a shard's first stream id, and
+        ``(seeds[i], stream_offset)`` with them, so message i equals ``sample_batch(1, lengths[i], contexts[i], ...,
+        seed=seeds[i], stream_offset=stream_offset)``.  Through ``slots`` slots (default ``min(B, max_batch)``) a
+        finished message's slot takes the next one, longest first; contexts are prefilled ragged into KV pages and
+        equal contexts and common prefixes share pages as in :meth:`encode_batch`.  Top-k values beyond the
+        single-pass limit (and "every id") form a second mixed group on the wide kernels, so a call has at most two
+        groups (``last_sample_schedule["quality_groups"]``).  Other LMs (any ``prefill`` / ``step`` object) run the
+        lockstep loop once per distinct (context, length, temperature, top-k), with the same draw keys."""
         import torch
 
+        if all(v is None for v in (contexts, lengths, temperatures, topks, seeds, slots, graphs)):
+            if context is None:
+                raise ConfigurationError("give exactly one of context (shared) and contexts (one per message)")
+        else:
+            return self._sample_streams(int(B), length, context, contexts, lengths, temperatures, topks, seeds, slots,
+                                        graphs, temperature, topk, seed, stream_offset, stats)
         params = CoderParams(vocab=self.vocab, precision=16, temp=float(temperature),
                              topk=int(topk) if int(topk) > 0 else self.vocab, dtype=self.logits_dtype,
                              banned=self.banned)
@@ -784,6 +811,127 @@ class HipArithmeticLM:
             if t + 1 < length:
                 logits = self.lm.step(tok.to(torch.long))
         return sess.tokens(), (sess.stats() if stats else None)
+
+    def _sample_streams(self, n, length, context, contexts, lengths, temperatures, topks, seeds, slots, graphs,
+                        temperature, topk, seed, stream_offset, stats):
+        """:meth:`sample_batch` with per-message values: validation (before any device use), the two top-k groups,
+        one :class:`SlotSampler` run per group on the native model, results back in the caller's order."""
+        context, contexts = _one_or_many(context, contexts, n)
+        lens, temps, tks = sample_plan(n, length, lengths, temperature, temperatures, topk, topks)
+        sds, gids = sample_draw_keys(n, seeds, seed, stream_offset)
+        if slots is not None and int(slots) < 1:
+            raise ConfigurationError("slots must be positive")
+        if n == 0:
+            self.last_sample_schedule = dict.fromkeys(SAMPLE_SCHEDULE_KEYS, 0)
+            return [], ([] if stats else None)
+        ctxs = contexts if contexts is not None else [list(context)] * n
+        groups = sample_topk_groups(tks, self._single_pass_limit())
+        plist = [CoderParams(vocab=self.vocab, precision=16, temp=temps[i], topk=tks[i] if tks[i] > 0 else self.vocab,
+                             dtype=self.logits_dtype, banned=self.banned) for i in range(n)]
+        toks: List[object] = [None] * n
+        sts: List[object] = [None] * n
+        sched = dict.fromkeys(SAMPLE_SCHEDULE_KEYS, 0)
+        native = getattr(self.lm, "native", False)
+        for members in groups:
+            sq = StreamQuality([plist[i] for i in members])
+            pick = lambda xs: [xs[i] for i in members]  # noqa: E731
+            if native:
+                from .slots import SlotSampler
+
+                S = max(1, min(len(members), int(slots) if slots else self.max_batch))
+                smp = SlotSampler(self, self._coder(sq.context_params(), S, mixed=True), pick(ctxs), pick(lens), sq,
+                                  pick(sds), pick(gids), slots=S, use_graph=graphs is None or bool(graphs),
+                                  stats=stats, compact=self.slot_compaction, share=self.share_contexts,
+                                  share_prefixes=self.share_prefixes)
+                res, st = smp.run()
+                sched["slots"] = max(sched["slots"], S)
+                sched["kv_pages_peak"] = max(sched["kv_pages_peak"], smp.kv_peak)
+                for k, v in (("prefill_rows", smp.prefill_rows), ("compactions", smp.compactions),
+                             ("evictions", smp.evictions)):
+                    sched[k] += v
+            else:
+                res, st = self._sample_lockstep(sq, pick(ctxs), pick(lens), pick(sds), pick(gids), stats)
+            for j, i in enumerate(members):
+                toks[i] = res[j]
+                if st is not None:
+                    sts[i] = st[j]
+        sched["quality_groups"] = len(groups)
+        self.last_sample_schedule = sched
+        return toks, (sts if stats else None)
+
+    def _sample_lockstep(self, sq, ctxs, lens, sds, gids, stats):
+        """Non-native LMs: the lockstep loop once per distinct (context, length, temperature, top-k) over that
+        group's messages, every message with its own draw key (``ns_sample_step_streams`` rows)."""
+        import torch
+
+        by: Dict[tuple, List[int]] = {}
+        for i, c in enumerate(ctxs):
+            q = sq.params[i]
+            by.setdefault((tuple(c[-1022:]), lens[i], q.temp, q.topk), []).append(i)
+        toks: List[object] = [None] * len(ctxs)
+        sts: List[object] = [None] * len(ctxs)
+        for (c, L, _, _), members in by.items():
+            B = len(members)
+            ctx = self._coder(sq.context_params(), B, mixed=True)
+            sess = SampleSession(ctx, B, max_tokens=L, stats=stats, quality=sq.take(members),
+                                 seeds=[sds[i] for i in members], gids=[gids[i] for i in members], lengths=[L] * B)
+            logits = self.lm.prefill(list(c), B, L + 1)
+            for t in range(L):
+                tok = sess.step(logits)
+                if t + 1 < L:
+                    logits = self.lm.step(tok.to(torch.long))
+            res, st = sess.tokens(), (sess.stats() if stats else None)
+            for j, i in enumerate(members):
+                toks[i] = res[j]
+                if st is not None:
+                    sts[i] = st[j]
+        return toks, (sts if stats else None)
+
+
+SAMPLE_SCHEDULE_KEYS = ("slots", "quality_groups", "prefill_rows", "compactions", "evictions", "kv_pages_peak")
+
+
+def sample_draw_keys(n: int, seeds, seed: int, stream_offset: int):
+    """``(seeds, draw ids)`` of the n messages of a ``sample_batch`` call: without ``seeds`` message i draws with
+    ``(seed, stream_offset + i)`` -- the lockstep call's rule, a shard being ``stream_offset`` -- and with them with
+    ``(seeds[i], stream_offset)``, what ``sample_batch(1, ..., seed=seeds[i], stream_offset=stream_offset)`` uses."""
+    off = int(stream_offset)
+    if seeds is None:
+        return [int(seed)] * n, [off + i for i in range(n)]
+    sds = [int(s) for s in seeds]
+    if len(sds) != n:
+        raise ConfigurationError(f"{len(sds)} seeds for {n} messages")
+    return sds, [off] * n
+
+
+def sample_plan(n: int, length, lengths, temperature, temperatures, topk, topks):
+    """Per-message ``(lengths, temperatures, topks)`` of a ``sample_batch`` call from the lists and the scalars
+    they default to; top-k as given (<= 0: every id).  A length below 1 is a ``ValueError`` (``sample.py:7`` asserts
+    ``length > 0``); a list of the wrong size and a temperature that is not positive are ConfigurationErrors."""
+    def many(name, values, default, conv):
+        if values is None:
+            return [conv(default)] * n
+        out = [conv(v) for v in values]
+        if len(out) != n:
+            raise ConfigurationError(f"{len(out)} {name} for {n} messages")
+        return out
+
+    lens = many("lengths", lengths, length, int)
+    temps = many("temperatures", temperatures, temperature, float)
+    tks = many("topks", topks, topk, int)
+    if any(v < 1 for v in lens):
+        raise ValueError("length must be positive")  # sample.py:7 asserts length > 0
+    if any(not v > 0 for v in temps):
+        raise ConfigurationError("temperature must be positive")
+    return lens, temps, tks
+
+
+def sample_topk_groups(topks: Sequence[int], limit: int) -> List[List[int]]:
+    """Message indices per slot run of a ``sample_batch`` call, grouped as :func:`_quality_groups` groups encode
+    qualities with ``mix_wide``: the messages whose top-k fits the single-pass kernel in one mixed group, the others
+    -- "every id" (top-k <= 0) among them, whatever the vocabulary -- in one more on the wide kernels."""
+    plist = [CoderParams(vocab=2, topk=int(k) if int(k) > 0 else (1 << 30)) for k in topks]
+    return _quality_groups(plist, limit, mix_wide=True)
 
 
 def _quality_groups(plist: Sequence[CoderParams], limit: int, mix_wide: bool = False) -> List[List[int]]:

@@ -1048,3 +1048,217 @@ class SlotDecoder:
         logits.index_copy_(0, idx, first.expand(n, -1).to(logits.dtype))
         slot_msg[slots] = msgs
         nlen_host[slots] = nl
+
+
+class SlotSampler:
+    """Sample ``lengths[m]`` tokens after ``contexts[m]`` for every message through ``slots`` slots, longest first.
+    Closest to :class:`SlotDecoder`: a message's end is known on the host from its length, so the loop never reads
+    the coder states -- a slot counts as finished once the event recorded at the previous check has passed with its
+    last token drawn.  On the device a stream past its length is PARKED by the step itself
+    (``ns_sample_step_streams``: nothing of it is written) and its attention is skipped through the per-stream stop
+    position, which is what lets ``check_every`` steps run without a host check.
+
+    Every message has its own context (a shared one is the same context N times: its pages are then shared), its
+    own row of the quality table (temperature, top-k) and of the draw table (seed, draw id, length).  Draws are keyed
+    by (seed, draw id, token index) and by nothing else, so a message gives the same tokens in any slot, and an
+    evicted message -- re-queued, restarted from token 0 -- gives them again."""
+
+    def __init__(self, provider, ctx, contexts: Sequence[Sequence[int]], lengths: Sequence[int], qualities, seeds,
+                 gids, *, slots: int, use_graph: bool, stats: bool, check_every: int = 16, compact: bool = True,
+                 share: bool = True, share_prefixes: bool = True):
+        self.p, self.lm, self.ctx = provider, provider.lm, ctx
+        self.qual = qualities  # coder.StreamQuality, one row per message
+        self.N = len(lengths)
+        self.S = max(1, min(int(slots), self.N))
+        self.lengths = np.asarray([int(v) for v in lengths], dtype=np.int64)
+        self.seeds, self.gids = [int(s) for s in seeds], [int(g) for g in gids]
+        self.contexts = _trimmed(contexts, self.N)
+        self.keys, self.shares = _multiplicity(self.contexts, share)
+        self.chains = _prefix_chains(self.contexts, share and share_prefixes and
+                                     getattr(self.lm, "prefix_sharing", False))
+        self.prefix_rows_saved = self.prefix_entries = 0
+        self.prefill_shared = self.prefill_rows = self.prefill_groups = 0
+        self.use_graph, self.stats = use_graph, stats
+        self.check_every, self.allow_compact = int(check_every), compact
+        self.compactions = self.evictions = self.kv_peak = 0
+
+    def run(self):
+        import torch
+
+        from ..coder import SampleSession
+
+        lm, S, N = self.lm, self.S, self.N
+        Lmax = int(self.lengths.max())
+        order = np.argsort(-self.lengths, kind="stable")  # longest first: the tail is short messages
+        # initial token-history / page-table width (both grow on demand; a provider may set a small one in tests)
+        budget = getattr(self.p, "slot_budget_tokens", None) or Lmax + 1
+        lm.begin_slots(S, 0, budget)
+        logits = torch.zeros((S, lm.ld), device=lm.device, dtype=lm.logits_dtype)
+        dev = logits.device
+        # every slot starts parked (length 0) on a valid quality row
+        sess = SampleSession(self.ctx, S, max_tokens=max(1, min(int(budget), Lmax)), stats=self.stats,
+                             quality=self.qual.take([0] * S), seeds=[0] * S, gids=[0] * S, lengths=[0] * S)
+        stop = torch.zeros(S, dtype=torch.int32, device=dev)
+        ctx_host = np.zeros(S, dtype=np.int64)
+        len_host = np.zeros(S, dtype=np.int64)
+        slot_msg = np.full(S, -1, dtype=np.int64)
+        queue = deque(order.tolist())
+        tokens: List[Optional[List[int]]] = [None] * N
+        stats_out: List[Optional[dict]] = [None] * N
+        graph, gkey = None, None
+        admit_blocked = False
+
+        def body():
+            lm.step_static(sess.step(logits))
+
+        def park(sl):
+            sess.park_slots(sl)
+            stop[torch.as_tensor(np.asarray(sl, dtype=np.int64), device=dev)] = 0
+            len_host[sl] = 0
+
+        t = 0
+        pipelined = self.use_graph
+        side = torch.cuda.Stream() if pipelined else None
+        pending = None
+        try:
+            while True:
+                if t % self.check_every == 0:
+                    live = slot_msg >= 0
+                    if pipelined:
+                        if pending is not None:
+                            ev, msg_then, fed_then = pending
+                            ev.synchronize()
+                            done = live & (slot_msg == msg_then) & (fed_then >= len_host)
+                        else:
+                            ev, done = None, np.zeros(slot_msg.shape, dtype=bool)
+                    else:
+                        ev, done = None, live & ((lm.kv.lens_host - ctx_host) >= len_host)
+                    fin = np.nonzero(done)[0]
+                    if fin.size:
+                        nl = len_host[fin]
+                        if ev is not None:
+                            host = _rows_after(ev, side, sess.hist, fin, int(nl.max())).numpy()
+                            acc = _rows_after(ev, side, sess.stats_acc, fin).numpy() if self.stats else None
+                            got = [host[j, : int(nl[j])].tolist() for j in range(fin.size)]
+                        else:
+                            got, acc = sess.harvest(fin, nl)
+                        for j, s in enumerate(fin.tolist()):
+                            m = int(slot_msg[s])
+                            tokens[m] = got[j]
+                            if self.stats:
+                                stats_out[m] = _stats_rows(acc[j:j + 1])[0]
+                        lm.kv.release(fin)
+                        slot_msg[fin] = -1
+                        park(fin)
+                        admit_blocked = False
+                        live = slot_msg >= 0
+                    empty = np.nonzero(~live)[0]
+                    if queue and empty.size and not admit_blocked:
+                        room = lm.pool.free_pages + lm.pool.growable_pages() - int(live.sum()) - 1
+                        adm = _admissible(queue, self.contexts, self.check_every, empty.size, room, self.keys,
+                                          self.shares, lm.kv.entries, self.chains, lm.kv.prefixes)
+                        if adm:
+                            back = self._admit_contexts(sess, logits, stop, empty[:len(adm)], adm, slot_msg, len_host,
+                                                        ctx_host)
+                            queue.extendleft(reversed(back))
+                            admit_blocked = bool(back)
+                            live = slot_msg >= 0
+                        if not live.any():
+                            m = queue[0]
+                            raise KVCapacityError(
+                                f"message {m}: no device memory for the KV pages of its "
+                                f"{len(self.contexts[m])}-token context")
+                    # pages for the next check_every + 1 positions (never past a message's last drawn token); on a
+                    # full device the youngest messages go back to the queue's front (sampled again from token 0:
+                    # the same tokens, their draws are keyed by seed, draw id and token index)
+                    while live.any():
+                        sl = np.nonzero(live)[0]
+                        upto = np.minimum(lm.kv.lens_host[sl] + self.check_every + 1, ctx_host[sl] + len_host[sl])
+                        if lm.kv.ensure(sl, upto).size == 0:
+                            break
+                        if sl.size == 1:
+                            raise KVCapacityError(f"message {int(slot_msg[sl[0]])} ({int(len_host[sl[0]])} tokens) "
+                                                  "needs more KV pages than the device holds")
+                        v = sl[np.argmin(lm.kv.lens_host[sl] - ctx_host[sl])]  # the youngest: fewest tokens drawn
+                        queue.appendleft(int(slot_msg[v]))
+                        lm.kv.release([v])
+                        park(np.asarray([v]))
+                        slot_msg[v] = -1
+                        live = slot_msg >= 0
+                        admit_blocked = True
+                        self.evictions += 1
+                    if not live.any():
+                        break
+                    if self.allow_compact and not queue and int(live.sum()) <= sess.B // 2 and sess.B > 1:
+                        keep = np.nonzero(live)[0]
+                        lm.kv.release(np.setdiff1d(np.arange(sess.B), keep))
+                        lm.kv.compact(keep)
+                        lm.B = lm.kv.B
+                        sess.compact(keep)
+                        ki = torch.as_tensor(keep, device=dev)
+                        stop = stop.index_select(0, ki).contiguous()
+                        logits = logits.index_select(0, ki).contiguous()
+                        slot_msg, len_host = slot_msg[keep].copy(), len_host[keep].copy()
+                        ctx_host = ctx_host[keep].copy()
+                        self.compactions += 1
+                    lm.stop_len = stop  # a parked slot skips its attention (and appends no K/V)
+                    if pipelined:
+                        ev_now = torch.cuda.Event()
+                        ev_now.record()
+                        pending = (ev_now, slot_msg.copy(), lm.kv.lens_host - ctx_host)
+                key = _layout_key(logits, sess.state, sess.hist, sess.out_token, sess.stats_acc, sess.qtable,
+                                  sess.draws, stop, lm.kv.table, lm.kv.lens) + (lm.kv.version,)
+                if self.use_graph:
+                    if graph is None or key != gkey:
+                        graph = None
+                        lm.begin_static(logits)
+                        graph, gkey = _SlotGraph(body), key
+                    else:
+                        graph.replay()
+                else:
+                    lm.begin_static(logits)
+                    body()
+                lm.advance(1)
+                t += 1
+        finally:
+            if graph is not None:
+                torch.cuda.current_stream().synchronize()
+            lm.stop_len = None
+            del graph
+        self.kv_peak = lm.kv.peak
+        return tokens, (stats_out if self.stats else None)
+
+    def _admit_contexts(self, sess, logits, stop, slots, msgs, slot_msg, len_host, ctx_host):
+        """Admit ``msgs`` into ``slots``: pages for each context and the message's first positions, one ragged prefill
+        of the contexts into those pages, the messages' quality and draw rows with fresh states, each context's
+        logits into its slot's row.  Returns the messages that could not be given pages (back to the queue)."""
+        import torch
+
+        lm = self.lm
+        slots = np.asarray(slots, dtype=np.int64)
+        tl = np.asarray([len(self.contexts[m]) for m in msgs], dtype=np.int64)
+        nl = self.lengths[np.asarray(msgs, dtype=np.int64)]
+        chains = [self.chains[m] for m in msgs] if self.chains is not None else None
+        ok = _map_contexts(lm.kv, slots, [self.keys[m] for m in msgs], [self.shares[m] for m in msgs], tl,
+                           tl + np.minimum(self.check_every + 1, nl), chains)
+        back = [m for m, k in zip(msgs, ok) if not k]
+        slots, msgs, tl, nl = slots[ok], [m for m, k in zip(msgs, ok) if k], tl[ok], nl[ok]
+        if not msgs:
+            return back
+        first = lm.prefill_contexts([self.contexts[m] for m in msgs], slots, [self.shares[m] for m in msgs],
+                                    [self.chains[m] for m in msgs] if self.chains is not None else None)
+        self.prefix_rows_saved += lm.last_prefill.get("prefix_rows_saved", 0)
+        self.prefix_entries += lm.last_prefill.get("prefix_entries", 0)
+        self.prefill_rows += lm.last_prefill["rows"]
+        self.prefill_groups += lm.last_prefill["groups"]
+        self.prefill_shared += lm.last_prefill["shared"]
+        sess.load_slots(slots, self.qual.take(msgs), [self.seeds[m] for m in msgs], [self.gids[m] for m in msgs], nl)
+        idx = torch.as_tensor(slots, device=logits.device)
+        # the attention is skipped once the cache length reaches context + length - 1: the logits after the last
+        # drawn token are never read
+        stop[idx] = torch.from_numpy((tl + nl - 1).astype(np.int32)).to(logits.device)
+        logits.index_copy_(0, idx, first.to(logits.dtype))
+        slot_msg[slots] = msgs
+        ctx_host[slots] = tl
+        len_host[slots] = nl
+        return back
