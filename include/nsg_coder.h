@@ -308,6 +308,45 @@ int ns_sample_step_streams(ns_ctx* ctx, const void* d_logits, int64_t ld, int B,
                            int32_t* d_token_hist, int64_t hist_stride, const int32_t* banned, int nbanned,
                            double* d_stats, ns_step_trace* d_trace, uint32_t step_flags, void* hip_stream);
 
+/* Per-stream quality row of the rank coder: everything one stream's rank step derives from (temp,
+ * ns_rank_quality).  One row per stream in DEVICE memory, written by the caller (no kernel writes the table).  The
+ * layout is fixed: 48 bytes, 8-byte aligned, fields at the offsets below. */
+typedef struct ns_rank_stream_quality {
+    double inv_temp;  /*  0: 1 / temp (the kernels divide by 1 / inv_temp, as the scalar entries do) */
+    double top_p;     /*  8: <= 0: off                                                   */
+    double min_prob;  /* 16: < 0: off                                                    */
+    double ptemp;     /* 24: prob_temp unless math.isclose(prob_temp, 1) or off: then 0  */
+    float c32;        /* 32: (float)(inv_temp * log2(e))                                 */
+    int32_t top_k;    /* 36: <= 0: off                                                   */
+    int32_t cap_bits; /* 40: <= 0: off                                                   */
+    int32_t crypto;   /* 44: 1 when prob_temp > 0 was given (isclose to 1 or not)        */
+} ns_rank_stream_quality;
+#define NS_RANK_STREAM_QUALITY_BYTES 48
+
+/* Fill one row on the host (pure arithmetic: no device, no context) with the checks and the derivations of the
+ * scalar rank steps.  NS_ERR_CONFIG unless temp > 0, top_p <= 1, and prob_temp > 0 comes with cap_bits and
+ * min_prob off. */
+int ns_rank_stream_quality_fill(double temp, const ns_rank_quality* quality, ns_rank_stream_quality* out_row);
+
+/* The rank steps with every stream's temperature and quality policy taken from row b of a DEVICE table given to the
+ * call itself: stream b performs the float64 operations of ns_rank_encode_step / ns_rank_decode_step called with the
+ * (temp, quality) its row was filled from, in the same order, so its tokens, consumption history, bits and trace
+ * (S included) are those of that call -- whatever row it runs in and whatever the other rows hold.  No host decision
+ * of the rank chain depends on the quality (every id is sorted under every policy), so a captured step stays valid
+ * whatever the rows hold.  A stream the step skips (NS_ST_DONE, an error flag, inactive on decode) writes nothing,
+ * but its row is still read: EVERY row [0, B) must be a valid filled row.  The other arguments are those of the
+ * scalar entries.  NS_ERR_CONFIG for a null or misaligned (8 bytes) table, a registered ns_set_stream_quality*
+ * table and a NS_DTYPE_F64 context (provider probability rows stay on the scalar entries). */
+int ns_rank_encode_step_streams(ns_ctx* ctx, const void* d_logits, int64_t ld, int B, const uint8_t* d_payload,
+                                int64_t payload_stride, const int64_t* d_payload_nbits, ns_stream_state* d_state,
+                                int32_t* d_out_token, int32_t* d_token_hist, int32_t* d_consumed_hist,
+                                int64_t hist_stride, const ns_rank_stream_quality* d_quality, ns_step_trace* d_trace,
+                                uint32_t step_flags, void* hip_stream);
+int ns_rank_decode_step_streams(ns_ctx* ctx, const void* d_logits, int64_t ld, int B, const int32_t* d_in_token,
+                                const int32_t* d_keep_bits, const uint8_t* d_active, ns_stream_state* d_state,
+                                uint8_t* d_out_bits, int64_t out_stride, const ns_rank_stream_quality* d_quality,
+                                ns_step_trace* d_trace, uint32_t step_flags, void* hip_stream);
+
 /* Rare-event diagnostics, cumulative since ns_create: counters[0] = stream-steps that took the exact-sum
  * path, counters[1] = candidate-buffer overflow compactions, counters[2] = speculative-threshold misses
  * (row re-read), counters[3] = top-K selections that left the histogram fast path (value ties or a skewed

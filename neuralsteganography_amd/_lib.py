@@ -30,6 +30,7 @@ EXPORTS = ("ns_create", "ns_destroy", "ns_last_error", "ns_version", "ns_max_top
            "ns_encode_step", "ns_decode_step", "ns_set_sentence_end", "ns_set_stats", "ns_sample_step", "ns_sample_step_streams",
            "ns_set_rank_export",
            "ns_rank_encode_step", "ns_set_rank_rows", "ns_rank_decode_step", "ns_token_probs",
+           "ns_rank_stream_quality_fill", "ns_rank_encode_step_streams", "ns_rank_decode_step_streams",
            "ns_stream_quality_fill", "ns_set_stream_quality", "ns_set_stream_quality_wide",
            "ns_read_counters", "ns_decode_attention", "ns_decode_attention_dev", "ns_decode_attention_prefix",
            "ns_decode_attention_fp8", "ns_decode_attention_ex", "ns_quantize_fp8",
@@ -84,6 +85,18 @@ NS_STREAM_QUALITY_BYTES = 32
 assert ctypes.sizeof(NsStreamQuality) == NS_STREAM_QUALITY_BYTES
 
 
+class NsRankStreamQuality(ctypes.Structure):
+    """``ns_rank_stream_quality`` (include/nsg_coder.h): one stream's rank-coder quality as the kernels read it."""
+
+    _fields_ = [("inv_temp", ctypes.c_double), ("top_p", ctypes.c_double), ("min_prob", ctypes.c_double),
+                ("ptemp", ctypes.c_double), ("c32", ctypes.c_float), ("top_k", ctypes.c_int32),
+                ("cap_bits", ctypes.c_int32), ("crypto", ctypes.c_int32)]
+
+
+NS_RANK_STREAM_QUALITY_BYTES = 48
+assert ctypes.sizeof(NsRankStreamQuality) == NS_RANK_STREAM_QUALITY_BYTES
+
+
 class NsSampleDraw(ctypes.Structure):
     """``ns_sample_draw`` (include/nsg_coder.h): what keys one sampler stream's draws, and its length."""
 
@@ -135,6 +148,15 @@ def lib() -> ctypes.CDLL:
     L.ns_rank_decode_step.restype = ctypes.c_int
     L.ns_rank_decode_step.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int64,
                                       ctypes.c_double, ctypes.POINTER(NsRankQuality), vp, ctypes.c_uint32, vp]
+    L.ns_rank_stream_quality_fill.restype = ctypes.c_int
+    L.ns_rank_stream_quality_fill.argtypes = [ctypes.c_double, ctypes.POINTER(NsRankQuality),
+                                              ctypes.POINTER(NsRankStreamQuality)]
+    L.ns_rank_encode_step_streams.restype = ctypes.c_int
+    L.ns_rank_encode_step_streams.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int, vp, ctypes.c_int64, vp, vp, vp,
+                                              vp, vp, ctypes.c_int64, vp, vp, ctypes.c_uint32, vp]
+    L.ns_rank_decode_step_streams.restype = ctypes.c_int
+    L.ns_rank_decode_step_streams.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int, vp, vp, vp, vp, vp,
+                                              ctypes.c_int64, vp, vp, ctypes.c_uint32, vp]
     L.ns_token_probs.restype = ctypes.c_int
     L.ns_token_probs.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_double,
                                  ctypes.POINTER(NsRankQuality), vp, ctypes.c_int64, vp, vp]

@@ -1116,3 +1116,342 @@ class RankDecodeSession:
             raise DecodeDivergenceError(f"streams {bad.tolist()[:8]}: token not present in distribution")
         ob = self.out_bits.cpu().numpy()
         return [ob[i, : int(f["bit_pos"][i]) // 8].tobytes() for i in range(self.B)]
+
+
+# ---------------------------------------------------------------------------------------------- rank coder, per stream
+def _rank_temp(quality) -> float:
+    """The softmax temperature of a rank quality mapping (``temp`` / ``temperature``, default 1), as the rank
+    provider reads it."""
+    for key in ("temp", "temperature"):
+        if quality and quality.get(key) is not None:
+            t = float(quality[key])
+            if t <= 0:
+                raise ConfigurationError("temperature must be positive")
+            return t
+    return 1.0
+
+
+def rank_stream_quality_rows(qualities, temps: Optional[Sequence[float]] = None) -> np.ndarray:
+    """``ns_rank_stream_quality`` rows as [n, 6] int64 (the 48-byte rows as the device table holds them), one per
+    quality mapping: keys and errors of :func:`rank_quality`, the temperature from the mapping (``temp`` /
+    ``temperature``) or from ``temps``; filled by the library's ``ns_rank_stream_quality_fill``."""
+    qs = list(qualities)
+    if temps is not None and len(temps) != len(qs):
+        raise ConfigurationError("one temperature per quality")
+    rows = np.zeros((len(qs), _lib.NS_RANK_STREAM_QUALITY_BYTES // 8), dtype=np.int64)
+    L = _lib.lib()
+    for i, q in enumerate(qs):
+        rq = q if isinstance(q, _lib.NsRankQuality) else rank_quality(q)
+        temp = float(temps[i]) if temps is not None else _rank_temp(None if isinstance(q, _lib.NsRankQuality) else q)
+        row = _lib.NsRankStreamQuality()
+        if L.ns_rank_stream_quality_fill(temp, ctypes.byref(rq), ctypes.byref(row)) != _lib.NS_OK:
+            raise ConfigurationError(f"quality {i}: {L.ns_last_error(None).decode()}")
+        rows[i] = np.frombuffer(bytes(row), dtype=np.int64)
+    return rows
+
+
+class RankStreamQuality:
+    """One ``ns_rank_stream_quality`` row per message (:func:`rank_stream_quality_rows`), as the slot loops take
+    them: :meth:`take` picks the rows of some messages, :meth:`table` puts them on a device."""
+
+    def __init__(self, rows: np.ndarray):
+        self.rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1, _lib.NS_RANK_STREAM_QUALITY_BYTES // 8)
+
+    @classmethod
+    def from_qualities(cls, qualities, temps=None) -> "RankStreamQuality":
+        return cls(rank_stream_quality_rows(qualities, temps))
+
+    def __len__(self) -> int:
+        return self.rows.shape[0]
+
+    def take(self, idx: Sequence[int]) -> "RankStreamQuality":
+        return RankStreamQuality(self.rows[np.asarray(list(idx), dtype=np.int64)])
+
+    def table(self, device):
+        return _torch().from_numpy(self.rows.copy()).to(device)
+
+
+_RANK_OFF_ROW = None
+
+
+def _rank_off_rows(n: int) -> RankStreamQuality:
+    """``n`` valid rows (temperature 1, every policy off): what an empty slot holds."""
+    global _RANK_OFF_ROW
+    if _RANK_OFF_ROW is None:
+        _RANK_OFF_ROW = rank_stream_quality_rows([{}])
+    return RankStreamQuality(np.repeat(_RANK_OFF_ROW, n, axis=0))
+
+
+class RankStreamEncodeSession:
+    """S slots of the rank coder with one quality row each (``ns_rank_encode_step_streams``): the slot operations of
+    :class:`EncodeSession` (:meth:`load_slots`, :meth:`park_slots`, :meth:`compact`, :meth:`ensure_history`) plus
+    :meth:`harvest`.  Every slot starts parked (NS_ST_DONE, no payload) on a valid row; with ``payloads`` and
+    ``quality`` the session starts with those streams loaded in slots 0..S-1."""
+
+    stats_acc = None  # the rank coder accumulates no statistics
+
+    def __init__(self, ctx: CoderContext, S: int, *, payload_stride: int = 1, max_tokens: int = 64,
+                 payloads: Optional[Sequence[bytes]] = None, quality: Optional[RankStreamQuality] = None):
+        torch = _torch()
+        self.ctx, self.B = ctx, int(S)
+        if self.B < 1 or self.B > ctx.max_batch:
+            raise ConfigurationError(f"batch {self.B} outside [1, {ctx.max_batch}]")
+        if ctx.params.dtype == "f64":
+            raise ConfigurationError("provider probability rows take one quality per call (no per-stream table)")
+        dev = torch.device("cuda", ctx.device)
+        stride = max(1, int(payload_stride), max((len(p) for p in payloads), default=1) if payloads else 1)
+        self.payload = torch.zeros((self.B, stride), dtype=torch.uint8, device=dev)
+        self.nbits = torch.zeros(self.B, dtype=torch.int64, device=dev)
+        self.state = _state_tensor(self.B, dev)
+        ctx.check(_lib.lib().ns_init_state(ctx._h, _ptr(self.state), self.B, _stream_handle()), "ns_init_state")
+        self.qtable = _rank_off_rows(self.B).table(dev)
+        self.out_token = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        cap = max(1, int(max_tokens))
+        self.hist = torch.full((self.B, cap), -1, dtype=torch.int32, device=dev)
+        self.cons = torch.zeros((self.B, cap), dtype=torch.int32, device=dev)
+        self.trace = None
+        self.park_slots(np.arange(self.B))
+        if payloads is not None:
+            if quality is None or len(payloads) != self.B:
+                raise ConfigurationError("one payload and one quality row per stream")
+            need = 8 * stride + 16
+            if need > cap:
+                self.ensure_history(need)
+            self.load_slots(np.arange(self.B), payloads, quality)
+
+    def enable_trace(self):
+        self.trace = _state_tensor(self.B, self.state.device)
+        return self.trace
+
+    def trace_rows(self) -> np.ndarray:
+        return _rank_trace_rows(self.trace, self.B)
+
+    def step(self, logits, *, finish_sent: bool = False):
+        if finish_sent:
+            raise ConfigurationError("the rank coder has no finish_sent")
+        _check_logits(self.ctx, self.B, logits)
+        rc = _lib.lib().ns_rank_encode_step_streams(
+            self.ctx._h, _ptr(logits), logits.stride(0), self.B, _ptr(self.payload), self.payload.stride(0),
+            _ptr(self.nbits), _ptr(self.state), _ptr(self.out_token), _ptr(self.hist), _ptr(self.cons),
+            self.hist.shape[1], _ptr(self.qtable), _ptr(self.trace), 0, _stream_handle())
+        self.ctx.check(rc, "ns_rank_encode_step_streams")
+        return self.out_token
+
+    def fields(self) -> dict:
+        return _state_fields(self.state)
+
+    def all_done(self) -> bool:
+        return bool(np.all((self.fields()["flags"] & _lib.NS_ST_DONE) != 0))
+
+    def raise_errors(self) -> None:
+        bad = np.nonzero(self.fields()["flags"] & _lib.NS_ST_ERR_RANGE)[0]
+        if bad.size:
+            raise ArithmeticRangeError(f"streams {bad.tolist()[:8]}: language model distribution provides no capacity")
+
+    def ensure_history(self, steps_ahead: int) -> None:
+        """Grow the token and consumption histories so ``steps_ahead`` more steps fit."""
+        need = int(self.fields()["ntokens"].max(initial=0)) + int(steps_ahead)
+        cap = self.hist.shape[1]
+        if need <= cap:
+            return
+        torch = _torch()
+        width = max(need, 2 * cap)
+        for name, fill in (("hist", -1), ("cons", 0)):
+            old = getattr(self, name)
+            new = torch.full((self.B, width), fill, dtype=torch.int32, device=old.device)
+            new[:, :cap] = old
+            setattr(self, name, new)
+
+    def load_slots(self, slots: Sequence[int], payloads: Sequence[object], quality: RankStreamQuality) -> None:
+        """Start new payloads in ``slots``: payload bytes (``bytes``, or the api's bit list -- LSB-first per byte, a
+        multiple of 8 long), bit count, a fresh state and the stream's quality row.  The history rows are reused from
+        position 0."""
+        torch = _torch()
+        n = len(slots)
+        if n == 0:
+            return
+        if quality is None or len(quality) != n or len(payloads) != n:
+            raise ConfigurationError("load_slots: one payload and one quality row per slot")
+        stride = self.payload.shape[1]
+        pl = np.zeros((n, stride), dtype=np.uint8)
+        nb = np.zeros(n, dtype=np.int64)
+        for i, p in enumerate(payloads):
+            if isinstance(p, (bytes, bytearray)):
+                packed = np.frombuffer(bytes(p), dtype=np.uint8)
+            else:
+                if len(p) % 8:
+                    raise ConfigurationError("bit stream length must be a multiple of 8")
+                packed = np.packbits(_bit_array(p) != 0, bitorder="little") if len(p) else np.zeros(0, np.uint8)
+            if packed.size > stride:
+                raise ConfigurationError("payload longer than the session's payload stride")
+            pl[i, : packed.size] = packed
+            nb[i] = 8 * packed.size
+        dev = self.state.device
+        idx = torch.as_tensor(np.asarray(slots, dtype=np.int64), device=dev)
+        self.payload[idx] = torch.from_numpy(pl).to(dev)
+        self.nbits[idx] = torch.from_numpy(nb).to(dev)
+        self.qtable[idx] = quality.table(dev)
+        self.state[idx] = torch.tensor([[0, 1 << self.ctx.params.precision, 0, 0]], dtype=torch.int64,
+                                       device=dev).expand(n, 4)
+
+    def park_slots(self, slots: Sequence[int]) -> None:
+        """Mark ``slots`` finished (NS_ST_DONE): the step writes nothing for them; their rows stay valid."""
+        if len(slots) == 0:
+            return
+        torch = _torch()
+        idx = torch.as_tensor(np.asarray(slots, dtype=np.int64), device=self.state.device)
+        w = self.state.view(torch.int32)
+        w[idx, 7] = w[idx, 7] | _lib.NS_ST_DONE
+
+    def compact(self, keep: Sequence[int]) -> None:
+        """Keep rows ``keep`` (in that order) of every per-stream buffer: the session now has len(keep) streams."""
+        torch = _torch()
+        idx = torch.as_tensor(np.asarray(keep, dtype=np.int64), device=self.state.device)
+        for name in ("payload", "nbits", "state", "out_token", "hist", "cons", "trace", "qtable"):
+            t = getattr(self, name)
+            if t is not None:
+                setattr(self, name, t.index_select(0, idx).contiguous())
+        self.B = len(keep)
+
+    def harvest(self, slots: Sequence[int]):
+        """``(token lists, consumed-bit lists)`` of ``slots`` (finished streams: the reference's tokens and
+        ``state["history"]``)."""
+        torch = _torch()
+        idx = torch.as_tensor(np.asarray(slots, dtype=np.int64), device=self.state.device)
+        nt = _state_fields(self.state.index_select(0, idx))["ntokens"]
+        return (_rows_to_lists(self.hist.index_select(0, idx), nt),
+                _rows_to_lists(self.cons.index_select(0, idx), nt))
+
+    def tokens(self) -> List[List[int]]:
+        self.raise_errors()
+        return self.harvest(np.arange(self.B))[0]
+
+    def consumed(self) -> List[List[int]]:
+        return self.harvest(np.arange(self.B))[1]
+
+
+class RankStreamDecodeSession:
+    """S slots of the rank decoder with one quality row each (``ns_rank_decode_step_streams``).  A slot holds its
+    message's tokens and keep-bits (the consumption history); a step decodes, for every slot, the token at the
+    slot's own index -- the stream's ``ntokens`` -- and a slot past its last token is inactive (nothing of it is
+    written), so the loop may run steps without a host check.  Every slot starts empty on a valid row."""
+
+    def __init__(self, ctx: CoderContext, S: int, *, max_tokens: int, max_bits: int,
+                 token_lists: Optional[Sequence[Sequence[int]]] = None,
+                 histories: Optional[Sequence[Sequence[int]]] = None, quality: Optional[RankStreamQuality] = None):
+        torch = _torch()
+        self.ctx, self.B = ctx, int(S)
+        if self.B < 1 or self.B > ctx.max_batch:
+            raise ConfigurationError(f"batch {self.B} outside [1, {ctx.max_batch}]")
+        if ctx.params.dtype == "f64":
+            raise ConfigurationError("provider probability rows take one quality per call (no per-stream table)")
+        dev = torch.device("cuda", ctx.device)
+        self.T = max(1, int(max_tokens))
+        self.tokmat = torch.zeros((self.B, self.T), dtype=torch.int32, device=dev)
+        self.keepmat = torch.zeros((self.B, self.T), dtype=torch.int32, device=dev)
+        self.nlen = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        self.out_stride = (max(0, int(max_bits)) + 7) // 8 + 8
+        self.out_bits = torch.zeros((self.B, self.out_stride), dtype=torch.uint8, device=dev)
+        self.state = _state_tensor(self.B, dev)
+        ctx.check(_lib.lib().ns_init_state(ctx._h, _ptr(self.state), self.B, _stream_handle()), "ns_init_state")
+        self.qtable = _rank_off_rows(self.B).table(dev)
+        self.trace = None
+        self._bufs = {}
+        if token_lists is not None:
+            if histories is None or quality is None or len(token_lists) != self.B:
+                raise ConfigurationError("one token list, one history and one quality row per stream")
+            self.load_slots(np.arange(self.B), token_lists, histories, quality)
+
+    def enable_trace(self):
+        self.trace = _state_tensor(self.B, self.state.device)
+        return self.trace
+
+    def trace_rows(self) -> np.ndarray:
+        return _rank_trace_rows(self.trace, self.B)
+
+    def step(self, logits):
+        """One decode step; returns the [B] tokens it fed (a slot past its end: its last token, inactive)."""
+        torch = _torch()
+        _check_logits(self.ctx, self.B, logits)
+        tix = self.state.view(torch.int32)[:, 6]  # ntokens: the index of the stream's next token
+        idx = tix.clamp(0, self.T - 1).long().unsqueeze(1)
+        tok = torch.gather(self.tokmat, 1, idx).squeeze(1).contiguous()
+        keep = torch.gather(self.keepmat, 1, idx).squeeze(1).contiguous()
+        act = (tix < self.nlen).to(torch.uint8)
+        self._bufs = {"tok": tok, "keep": keep, "act": act}  # alive until the next step (graph replays reuse them)
+        rc = _lib.lib().ns_rank_decode_step_streams(
+            self.ctx._h, _ptr(logits), logits.stride(0), self.B, _ptr(tok), _ptr(keep), _ptr(act), _ptr(self.state),
+            _ptr(self.out_bits), self.out_stride, _ptr(self.qtable), _ptr(self.trace), 0, _stream_handle())
+        self.ctx.check(rc, "ns_rank_decode_step_streams")
+        return tok
+
+    def load_slots(self, slots: Sequence[int], token_lists: Sequence[Sequence[int]],
+                   histories: Sequence[Sequence[int]], quality: RankStreamQuality) -> None:
+        """Start new messages in ``slots``: tokens, keep-bits, token count, zeroed output bytes, a fresh state and
+        the stream's quality row."""
+        torch = _torch()
+        n = len(slots)
+        if n == 0:
+            return
+        if quality is None or len(quality) != n or len(token_lists) != n or len(histories) != n:
+            raise ConfigurationError("load_slots: one token list, one history and one quality row per slot")
+        tok = np.zeros((n, self.T), dtype=np.int32)
+        keep = np.zeros((n, self.T), dtype=np.int32)
+        nl = np.zeros(n, dtype=np.int32)
+        for i, (tl, hs) in enumerate(zip(token_lists, histories)):
+            k = len(tl)
+            if len(hs) < k:
+                raise DecodeDivergenceError("Bit consumption history is required for decoding")
+            if k > self.T or sum(list(hs)[:k]) > 8 * (self.out_stride - 8):
+                raise ConfigurationError("message longer than the session was sized for")
+            tok[i, :k] = np.asarray(tl, dtype=np.int32)
+            keep[i, :k] = np.asarray(list(hs)[:k], dtype=np.int32)
+            nl[i] = k
+        dev = self.state.device
+        idx = torch.as_tensor(np.asarray(slots, dtype=np.int64), device=dev)
+        self.tokmat[idx] = torch.from_numpy(tok).to(dev)
+        self.keepmat[idx] = torch.from_numpy(keep).to(dev)
+        self.nlen[idx] = torch.from_numpy(nl).to(dev)
+        self.out_bits[idx] = 0
+        self.qtable[idx] = quality.table(dev)
+        self.state[idx] = torch.tensor([[0, 1 << self.ctx.params.precision, 0, 0]], dtype=torch.int64,
+                                       device=dev).expand(n, 4)
+
+    def park_slots(self, slots: Sequence[int]) -> None:
+        """Empty ``slots`` (token count 0): the step leaves them inactive."""
+        if len(slots) == 0:
+            return
+        torch = _torch()
+        idx = torch.as_tensor(np.asarray(slots, dtype=np.int64), device=self.state.device)
+        self.nlen[idx] = 0
+
+    def compact(self, keep: Sequence[int]) -> None:
+        torch = _torch()
+        idx = torch.as_tensor(np.asarray(keep, dtype=np.int64), device=self.state.device)
+        for name in ("tokmat", "keepmat", "nlen", "out_bits", "state", "trace", "qtable"):
+            t = getattr(self, name)
+            if t is not None:
+                setattr(self, name, t.index_select(0, idx).contiguous())
+        self.B = len(keep)
+
+    @staticmethod
+    def payloads_of(state_rows, out_rows) -> List[bytes]:
+        """The decoded bytes of host copies of some slots' state and output rows (whole bytes only, as
+        :meth:`RankDecodeSession.payloads` returns them)."""
+        f = _state_fields(state_rows)
+        ob = out_rows.cpu().numpy()
+        return [ob[i, : int(f["bit_pos"][i]) // 8].tobytes() for i in range(ob.shape[0])]
+
+    def harvest(self, slots: Sequence[int]):
+        """``(payload bytes, flags)`` of ``slots``."""
+        torch = _torch()
+        idx = torch.as_tensor(np.asarray(slots, dtype=np.int64), device=self.state.device)
+        st = self.state.index_select(0, idx)
+        return self.payloads_of(st, self.out_bits.index_select(0, idx)), _state_fields(st)["flags"]
+
+    def payloads(self) -> List[bytes]:
+        pls, flags = self.harvest(np.arange(self.B))
+        bad = np.nonzero(flags & _lib.NS_ST_ERR_DIVERGE)[0]
+        if bad.size:
+            raise DecodeDivergenceError(f"streams {bad.tolist()[:8]}: token not present in distribution")
+        return pls

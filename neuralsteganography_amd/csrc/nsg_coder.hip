@@ -1707,7 +1707,7 @@ static bool launch(ns_ctx* ctx, const nsg::StepParams& p, hipStream_t s) {
 
 extern "C" {
 
-const char* ns_version(void) { return "nsgcoder 0.31.4 gfx950"; }
+const char* ns_version(void) { return "nsgcoder 0.31.5 gfx950"; }
 
 int ns_set_split_max_batch(int max_batch) {
     const int prev = split_setting();
@@ -1997,10 +1997,43 @@ int ns_sample_step_streams(ns_ctx* ctx, const void* d_logits, int64_t ld, int B,
     return NS_OK;
 }
 
+// crypto/quality.py:60: the temperature step runs unless math.isclose(T, 1.0) (rel_tol 1e-9)
+static double rank_ptemp(double pt) { return (pt > 0.0 && fabs(pt - 1.0) > 1e-9 * fmax(pt, 1.0)) ? pt : 0.0; }
+
+int ns_rank_stream_quality_fill(double temp, const ns_rank_quality* q, ns_rank_stream_quality* out_row) {
+    if (!q || !out_row) return fail(nullptr, NS_ERR_CONFIG, "ns_rank_stream_quality_fill: bad argument");
+    if (q->top_p > 1.0) return fail(nullptr, NS_ERR_CONFIG, "top_p must be within (0, 1]");
+    if (q->prob_temp > 0.0 && (q->cap_bits > 0 || q->min_prob >= 0.0))
+        return fail(nullptr, NS_ERR_CONFIG, "crypto quality (prob_temp) takes only top_k and top_p");
+    if (!(temp > 0.0)) return fail(nullptr, NS_ERR_CONFIG, "temperature must be positive");
+    ns_rank_stream_quality row;
+    row.inv_temp = 1.0 / temp;  // prepare()'s own expressions: the kernels then divide by the same 1 / inv_temp
+    row.c32 = (float)(row.inv_temp * 1.4426950408889634);
+    row.top_p = q->top_p;
+    row.min_prob = q->min_prob;
+    row.ptemp = rank_ptemp(q->prob_temp);
+    row.top_k = q->top_k;
+    row.cap_bits = q->cap_bits;
+    row.crypto = q->prob_temp > 0.0 ? 1 : 0;
+    *out_row = row;
+    return NS_OK;
+}
+
+// q: the call's scalar quality, or d_rows: one row per stream (ns_rank_*_step_streams; temp is then unused)
 static int rank_prepare(ns_ctx* ctx, nsg::StepParams& p, const void* d_logits, int64_t ld, int B, double temp,
-                        const ns_rank_quality* q, ns_step_trace* d_trace, uint32_t flags, ns_stream_state* d_state) {
+                        const ns_rank_quality* q, ns_step_trace* d_trace, uint32_t flags, ns_stream_state* d_state,
+                        const ns_rank_stream_quality* d_rows = nullptr, bool streams = false) {
     if (!ctx) return fail(ctx, NS_ERR_CONFIG, "null context");
     if (ctx->quality) return fail(ctx, NS_ERR_CONFIG, "rank step: a stream quality table is registered");
+    if (streams) {
+        if (ctx->dtype == NS_DTYPE_F64)
+            return fail(ctx, NS_ERR_CONFIG, "rank step: provider probability rows (NS_DTYPE_F64) take no quality table");
+        if (!d_rows || ((uintptr_t)d_rows & 7u) != 0u)
+            return fail(ctx, NS_ERR_CONFIG, "rank step: the quality table must be non-null and 8-byte aligned");
+        static const ns_rank_quality off = {0, 0, 0.0, -1.0, 0.0};
+        q = &off;  // the scalars are not read by a kernel once rk_rows is set
+        temp = 1.0;
+    }
     if (!q) return fail(ctx, NS_ERR_CONFIG, "rank step: null quality");
     if (q->top_p > 1.0) return fail(ctx, NS_ERR_CONFIG, "top_p must be within (0, 1]");
     if (q->prob_temp > 0.0 && (q->cap_bits > 0 || q->min_prob >= 0.0))
@@ -2019,10 +2052,9 @@ static int rank_prepare(ns_ctx* ctx, nsg::StepParams& p, const void* d_logits, i
     p.rk_cap = q->cap_bits;
     p.rk_top_p = q->top_p;
     p.rk_min_prob = q->min_prob;
-    // crypto/quality.py:60: the temperature step runs unless math.isclose(T, 1.0) (rel_tol 1e-9)
-    const double pt = q->prob_temp;
-    p.rk_ptemp = (pt > 0.0 && fabs(pt - 1.0) > 1e-9 * fmax(pt, 1.0)) ? pt : 0.0;
-    p.rk_crypto = pt > 0.0 ? 1 : 0;
+    p.rk_ptemp = rank_ptemp(q->prob_temp);
+    p.rk_crypto = q->prob_temp > 0.0 ? 1 : 0;
+    p.rk_rows = d_rows;
     if (ctx->dtype == NS_DTYPE_F64) {
         p.rk_count = ctx->rk_count;
         p.rk_idmap = ctx->rk_idmap;
@@ -2032,13 +2064,14 @@ static int rank_prepare(ns_ctx* ctx, nsg::StepParams& p, const void* d_logits, i
     return NS_OK;
 }
 
-int ns_rank_encode_step(ns_ctx* ctx, const void* d_logits, int64_t ld, int B, const uint8_t* d_payload,
-                        int64_t payload_stride, const int64_t* d_payload_nbits, ns_stream_state* d_state,
-                        int32_t* d_out_token, int32_t* d_token_hist, int32_t* d_consumed_hist, int64_t hist_stride,
-                        double temp, const ns_rank_quality* quality, ns_step_trace* d_trace, uint32_t step_flags,
-                        void* hip_stream) {
+static int rank_encode_step(ns_ctx* ctx, const void* d_logits, int64_t ld, int B, const uint8_t* d_payload,
+                            int64_t payload_stride, const int64_t* d_payload_nbits, ns_stream_state* d_state,
+                            int32_t* d_out_token, int32_t* d_token_hist, int32_t* d_consumed_hist,
+                            int64_t hist_stride, double temp, const ns_rank_quality* quality,
+                            const ns_rank_stream_quality* d_rows, bool streams, ns_step_trace* d_trace,
+                            uint32_t step_flags, void* hip_stream) {
     nsg::StepParams p;
-    int rc = rank_prepare(ctx, p, d_logits, ld, B, temp, quality, d_trace, step_flags, d_state);
+    int rc = rank_prepare(ctx, p, d_logits, ld, B, temp, quality, d_trace, step_flags, d_state, d_rows, streams);
     if (rc != NS_OK) return rc;
     if (!d_payload || !d_payload_nbits || !d_out_token || payload_stride < 0)
         return fail(ctx, NS_ERR_CONFIG, "ns_rank_encode_step: null payload/out pointer");
@@ -2054,12 +2087,13 @@ int ns_rank_encode_step(ns_ctx* ctx, const void* d_logits, int64_t ld, int B, co
     return NS_OK;
 }
 
-int ns_rank_decode_step(ns_ctx* ctx, const void* d_logits, int64_t ld, int B, const int32_t* d_in_token,
-                        const int32_t* d_keep_bits, const uint8_t* d_active, ns_stream_state* d_state,
-                        uint8_t* d_out_bits, int64_t out_stride, double temp, const ns_rank_quality* quality,
-                        ns_step_trace* d_trace, uint32_t step_flags, void* hip_stream) {
+static int rank_decode_step(ns_ctx* ctx, const void* d_logits, int64_t ld, int B, const int32_t* d_in_token,
+                            const int32_t* d_keep_bits, const uint8_t* d_active, ns_stream_state* d_state,
+                            uint8_t* d_out_bits, int64_t out_stride, double temp, const ns_rank_quality* quality,
+                            const ns_rank_stream_quality* d_rows, bool streams, ns_step_trace* d_trace,
+                            uint32_t step_flags, void* hip_stream) {
     nsg::StepParams p;
-    int rc = rank_prepare(ctx, p, d_logits, ld, B, temp, quality, d_trace, step_flags, d_state);
+    int rc = rank_prepare(ctx, p, d_logits, ld, B, temp, quality, d_trace, step_flags, d_state, d_rows, streams);
     if (rc != NS_OK) return rc;
     if (!d_in_token || !d_keep_bits || !d_out_bits || out_stride < 1)
         return fail(ctx, NS_ERR_CONFIG, "ns_rank_decode_step: null token/out pointer");
@@ -2071,6 +2105,42 @@ int ns_rank_decode_step(ns_ctx* ctx, const void* d_logits, int64_t ld, int B, co
     if (!nsg_rank_launch(ctx, p, true, (hipStream_t)hip_stream))
         return fail(ctx, NS_ERR_HIP, "ns_rank_decode_step: launch failed");
     return NS_OK;
+}
+
+int ns_rank_encode_step(ns_ctx* ctx, const void* d_logits, int64_t ld, int B, const uint8_t* d_payload,
+                        int64_t payload_stride, const int64_t* d_payload_nbits, ns_stream_state* d_state,
+                        int32_t* d_out_token, int32_t* d_token_hist, int32_t* d_consumed_hist, int64_t hist_stride,
+                        double temp, const ns_rank_quality* quality, ns_step_trace* d_trace, uint32_t step_flags,
+                        void* hip_stream) {
+    return rank_encode_step(ctx, d_logits, ld, B, d_payload, payload_stride, d_payload_nbits, d_state, d_out_token,
+                            d_token_hist, d_consumed_hist, hist_stride, temp, quality, nullptr, false, d_trace,
+                            step_flags, hip_stream);
+}
+
+int ns_rank_decode_step(ns_ctx* ctx, const void* d_logits, int64_t ld, int B, const int32_t* d_in_token,
+                        const int32_t* d_keep_bits, const uint8_t* d_active, ns_stream_state* d_state,
+                        uint8_t* d_out_bits, int64_t out_stride, double temp, const ns_rank_quality* quality,
+                        ns_step_trace* d_trace, uint32_t step_flags, void* hip_stream) {
+    return rank_decode_step(ctx, d_logits, ld, B, d_in_token, d_keep_bits, d_active, d_state, d_out_bits, out_stride,
+                            temp, quality, nullptr, false, d_trace, step_flags, hip_stream);
+}
+
+int ns_rank_encode_step_streams(ns_ctx* ctx, const void* d_logits, int64_t ld, int B, const uint8_t* d_payload,
+                                int64_t payload_stride, const int64_t* d_payload_nbits, ns_stream_state* d_state,
+                                int32_t* d_out_token, int32_t* d_token_hist, int32_t* d_consumed_hist,
+                                int64_t hist_stride, const ns_rank_stream_quality* d_quality, ns_step_trace* d_trace,
+                                uint32_t step_flags, void* hip_stream) {
+    return rank_encode_step(ctx, d_logits, ld, B, d_payload, payload_stride, d_payload_nbits, d_state, d_out_token,
+                            d_token_hist, d_consumed_hist, hist_stride, 1.0, nullptr, d_quality, true, d_trace,
+                            step_flags, hip_stream);
+}
+
+int ns_rank_decode_step_streams(ns_ctx* ctx, const void* d_logits, int64_t ld, int B, const int32_t* d_in_token,
+                                const int32_t* d_keep_bits, const uint8_t* d_active, ns_stream_state* d_state,
+                                uint8_t* d_out_bits, int64_t out_stride, const ns_rank_stream_quality* d_quality,
+                                ns_step_trace* d_trace, uint32_t step_flags, void* hip_stream) {
+    return rank_decode_step(ctx, d_logits, ld, B, d_in_token, d_keep_bits, d_active, d_state, d_out_bits, out_stride,
+                            1.0, nullptr, d_quality, true, d_trace, step_flags, hip_stream);
 }
 
 int ns_token_probs(ns_ctx* ctx, const void* d_logits, int64_t ld, int B, double temp, const ns_rank_quality* quality,

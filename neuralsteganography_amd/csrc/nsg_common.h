@@ -323,6 +323,9 @@ struct StepParams {
     // per-stream draw rows of the sampler (ns_sample_step_streams), nullable: then seed and stream_offset + b above
     // key the draw and no stream is parked
     const ns_sample_draw* draws;
+    // per-stream quality rows of the rank coder (ns_rank_*_step_streams), nullable: then inv_temp, c32 and the rk_
+    // policy fields above hold for every stream
+    const ns_rank_stream_quality* rk_rows;
 };
 
 // The quality of stream b (wave-uniform): its table row, or the call's scalars.  b is wave-uniform, so the row is
@@ -346,6 +349,35 @@ __device__ __forceinline__ RowQuality row_quality(const StepParams& p, int b) {
         q.topk = __builtin_amdgcn_readfirstlane(row.topk);
         q.K = min(max(__builtin_amdgcn_readfirstlane(row.K), 1), p.K);
         q.spec_j = __builtin_amdgcn_readfirstlane(row.spec_j);
+    }
+    return q;
+}
+
+// The rank coder's quality of stream b (b wave-uniform; block-uniform where a block serves one stream): its
+// ns_rank_stream_quality row, or the call's scalars.  Read once at entry, every field pinned to scalar registers.
+struct RankQuality {
+    double inv_temp, top_p, min_prob, ptemp;
+    float c32;
+    int top_k, cap, crypto;
+};
+__device__ __forceinline__ double uniform_f64(double v) {
+    const uint64_t u = __builtin_bit_cast(uint64_t, v);
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
+    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ RankQuality rank_quality_of(const StepParams& p, int b) {
+    RankQuality q{p.inv_temp, p.rk_top_p, p.rk_min_prob, p.rk_ptemp, p.c32, p.rk_top_k, p.rk_cap, p.rk_crypto};
+    if (p.rk_rows) {
+        const ns_rank_stream_quality row = p.rk_rows[b];
+        q.inv_temp = uniform_f64(row.inv_temp);
+        q.top_p = uniform_f64(row.top_p);
+        q.min_prob = uniform_f64(row.min_prob);
+        q.ptemp = uniform_f64(row.ptemp);
+        q.c32 = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(row.c32)));
+        q.top_k = __builtin_amdgcn_readfirstlane(row.top_k);
+        q.cap = __builtin_amdgcn_readfirstlane(row.cap_bits);
+        q.crypto = __builtin_amdgcn_readfirstlane(row.crypto);
     }
     return q;
 }

@@ -20,7 +20,8 @@
 // With a stream quality table (ns_set_stream_quality_wide) steps 1 and 3 take stream b's temperature, topk, K and
 // precision from row b (row_quality, read once per stream); a row's K may be anything in [1, k_max] -- it only
 // shortens the ranks the cutoff looks at.  The launches follow the call's k_max alone.
-// Rank coder (ns_rank_*_step, scalar quality only): wide_stats_kernel (wave per stream) -> wide_collect_kernel
+// Rank coder (ns_rank_*_step; ns_rank_*_step_streams: stream b's temperature and policy from row b of the call's
+// table, rank_quality_of, read once per block): wide_stats_kernel (wave per stream) -> wide_collect_kernel
 // (blocks per chunk, every valid id) -> the device-wide sort -> wide_rank_kernel.
 // An id left out of the collection has e_i < S_lo/R <= S/R, i.e. p_i < 1/R for certain, so the first rank
 // below the cutoff lies inside the collected prefix or right after it.
@@ -71,6 +72,7 @@ __global__ __launch_bounds__(WPB* WAVE) void wide_stats_kernel(StepParams p, Wid
         return;
     }
     const int V = p.V;
+    const RankQuality rq = rank_quality_of(p, b);  // stream b's temperature (its row, or the call's)
     const char* rowc = (const char*)p.logits + (int64_t)b * p.ld * (int64_t)sizeof(T);
     const RowReader rd(rowc, (uint32_t)(p.ld * (int64_t)sizeof(T)));
     const int ntiles = (V + TS - 1) / TS;
@@ -105,7 +107,7 @@ __global__ __launch_bounds__(WPB* WAVE) void wide_stats_kernel(StepParams p, Wid
 #pragma unroll
         for (int q = 0; q < W; ++q) {
             const float dx = fmaxf(x[q] - r, -3.0e38f);
-            const float e = __builtin_amdgcn_exp2f(dx * p.c32);
+            const float e = __builtin_amdgcn_exp2f(dx * rq.c32);
             a += e;
             if (stats) {
                 bb += e * dx;
@@ -128,7 +130,7 @@ __global__ __launch_bounds__(WPB* WAVE) void wide_stats_kernel(StepParams p, Wid
     const double B_r = wave_sum_butterfly(b64);
     const double U_r = wave_sum_butterfly(u64);
     double Sf = 0.0, S_lo = 0.0, S_hi = 0.0;
-    const bool ok = fast_sum_interval(S_r, r, (double)(m1 + 0.0f), p.c32, p.inv_temp, W, Sf, S_lo, S_hi);
+    const bool ok = fast_sum_interval(S_r, r, (double)(m1 + 0.0f), rq.c32, rq.inv_temp, W, Sf, S_lo, S_hi);
     if (lane == 0) {
         WideStat w;
         w.m = m1;
@@ -1698,11 +1700,11 @@ __global__ __launch_bounds__(FAST_THREADS, NSG_FAST_WAVES_PER_SIMD) void wide_on
 
 // R2: top_k, top_p (left-to-right cumsum over ranks [0, V), searchsorted 'left'), min_prob cut the support [0, n)
 template <class PF>
-__device__ int rank_quality_cut(const StepParams& p, int V, int n, PF&& pf, double* ebuf, int* smi, int& cut_sh,
+__device__ int rank_quality_cut(const RankQuality& q, int V, int n, PF&& pf, double* ebuf, int* smi, int& cut_sh,
                                 double& acc_sh) {
     const int tid = threadIdx.x;
-    if (p.rk_top_k > 0) n = min(n, p.rk_top_k);
-    if (p.rk_top_p > 0.0) {
+    if (q.top_k > 0) n = min(n, q.top_k);
+    if (q.top_p > 0.0) {
         if (tid == 0) {
             cut_sh = V;
             acc_sh = 0.0;
@@ -1715,7 +1717,7 @@ __device__ int rank_quality_cut(const StepParams& p, int V, int n, PF&& pf, doub
                 double a = acc_sh;
                 for (int i = 0; i < WIDE_ROUND && base + i < V; ++i) {
                     a += ebuf[i];
-                    if (a >= p.rk_top_p) {
+                    if (a >= q.top_p) {
                         cut_sh = base + i;
                         break;
                     }
@@ -1728,10 +1730,10 @@ __device__ int rank_quality_cut(const StepParams& p, int V, int n, PF&& pf, doub
         n = min(n, min(cut_sh + 1, V));
         __syncthreads();
     }
-    if (p.rk_min_prob >= 0.0) {
+    if (q.min_prob >= 0.0) {
         int fm = V;
         for (int i = tid; i < V; i += WIDE_THREADS)
-            if (i < fm && !(pf(i) >= p.rk_min_prob)) fm = i;
+            if (i < fm && !(pf(i) >= q.min_prob)) fm = i;
         n = min(n, block_min_int(fm, smi));
     }
     return n;
@@ -1740,9 +1742,9 @@ __device__ int rank_quality_cut(const StepParams& p, int V, int n, PF&& pf, doub
 // R3: cap_per_token_bits -- entropy of the renormalised support; bisect tau on softmax(log(f+1e-12)/tau) over the
 // universe of U ranks (float64, libm-equivalent log/exp: tolerance-level); returns the new support
 template <class PF>
-__device__ int rank_cap(const StepParams& p, int U, int n, PF&& pf, double* sm64, int* smi) {
+__device__ int rank_cap(const RankQuality& q, int U, int n, PF&& pf, double* sm64, int* smi) {
     const int tid = threadIdx.x;
-    if (!(p.rk_cap > 0 && n > 0)) return n;
+    if (!(q.cap > 0 && n > 0)) return n;
     double fl = 0.0;
     for (int i = tid; i < n; i += WIDE_THREADS) fl += pf(i);
     const double F = block_sum(fl, sm64);
@@ -1752,7 +1754,7 @@ __device__ int rank_cap(const StepParams& p, int U, int n, PF&& pf, double* sm64
         if (f > 0.0) hl -= f * log2(f);
     }
     const double H = block_sum(hl, sm64);
-    if (!(H > (double)p.rk_cap)) return n;
+    if (!(H > (double)q.cap)) return n;
     const double lf0 = log(pf(0) / F + 1e-12);
     double low = 1e-6, high = 1.0;
     int n_target = n;
@@ -1776,7 +1778,7 @@ __device__ int rank_cap(const StepParams& p, int U, int n, PF&& pf, double* sm64
         const double t = block_sum(tl, sm64);
         const int nz = block_min_int(zl, smi);
         const double Hc = (log(s) - t / s) / 0.6931471805599453;  // entropy of c/s in bits
-        if (Hc > (double)p.rk_cap) {
+        if (Hc > (double)q.cap) {
             high = mid;
         } else {
             low = mid;
@@ -1875,7 +1877,8 @@ __global__ __launch_bounds__(WIDE_THREADS) void wide_rank_kernel(StepParams p, c
     const ns_stream_state st = p.state[b];
     const uint64_t* sk = keys_sorted + (int64_t)b * cap;
     const int V = (int)count[b];
-    const double temp = 1.0 / p.inv_temp;
+    const RankQuality rq = rank_quality_of(p, b);  // block-uniform: stream b's row, or the call's scalars
+    const double temp = 1.0 / rq.inv_temp;
     const double zmax = (double)wkey_val(sk[0]) / temp;
     auto e_of = [&](int i) -> double { return exp_canon((double)wkey_val(sk[i]) / temp - zmax); };
 
@@ -1900,7 +1903,7 @@ __global__ __launch_bounds__(WIDE_THREADS) void wide_rank_kernel(StepParams p, c
     // R1c: crypto quality LM (crypto/quality.py:57-64): temperature on the probabilities,
     // q_i = exp(log(p_i + 1e-12)/T - max) normalised -- every id keeps mass unless exp underflows.
     // Monotone in p, so the rank order is unchanged; libm-equivalent log/exp (tolerance-level).
-    const double Tq = p.rk_ptemp;
+    const double Tq = rq.ptemp;
     const bool crypto = Tq > 0.0;
     double a0 = 0.0, Q = 1.0;
     if (crypto) {
@@ -1917,10 +1920,10 @@ __global__ __launch_bounds__(WIDE_THREADS) void wide_rank_kernel(StepParams p, c
     }
     auto pf = [&](int i) -> double { return crypto ? exp(log(p_of(i) + 1e-12) / Tq - a0) / Q : p_of(i); };
 
-    n = rank_quality_cut(p, V, n, pf, ebuf, smi, cut_sh, acc_sh);
+    n = rank_quality_cut(rq, V, n, pf, ebuf, smi, cut_sh, acc_sh);
     // next_token_probs (codec/distribution.py:107-142): the quality-filtered support renormalised, by id
     if (p.probs_out) {
-        const bool filtered = p.rk_top_k > 0 || p.rk_top_p > 0.0 || p.rk_min_prob >= 0.0;
+        const bool filtered = rq.top_k > 0 || rq.top_p > 0.0 || rq.min_prob >= 0.0;
         const int keep = filtered ? n : V;
         double fl = 0.0;
         for (int i = tid; i < keep; i += WIDE_THREADS) fl += pf(i);
@@ -1931,7 +1934,7 @@ __global__ __launch_bounds__(WIDE_THREADS) void wide_rank_kernel(StepParams p, c
         for (int i = tid; i < keep; i += WIDE_THREADS) out[wkey_id(sk[i])] = pf(i) / F;
         return;
     }
-    n = rank_cap(p, V, n, pf, sm64, smi);
+    n = rank_cap(rq, V, n, pf, sm64, smi);
     uint64_t kt = 0;  // decode: the received token's key
     if (DECODE) {
         const int32_t tok = p.in_token[b];
@@ -2116,8 +2119,9 @@ __global__ __launch_bounds__(WIDE_THREADS) void wide_rank64_kernel(StepParams p,
     auto np_sum = [&](auto&& f) -> double { return block_np_sum(N, f, ebuf, lstart, llen, &nleaf_sh); };
 
     // P1: crypto policy: p = v / np.sum(v), then (unless isclose(T, 1)) tempered and renormalised
-    const bool crypto = p.rk_crypto != 0;
-    const double Tq = p.rk_ptemp;
+    const RankQuality rq = rank_quality_of(p, b);  // provider rows take the call's scalars (no table on this path)
+    const bool crypto = rq.crypto != 0;
+    const double Tq = rq.ptemp;
     double tot = 1.0, a0 = 0.0, Q = 1.0;
     if (crypto) {
         tot = np_sum([&](int j) -> double { return row[j]; });
@@ -2141,10 +2145,10 @@ __global__ __launch_bounds__(WIDE_THREADS) void wide_rank64_kernel(StepParams p,
     for (int i = tid; i < N; i += WIDE_THREADS)
         if (i < fz && !(pf(i) > 0.0)) fz = i;
     int n = block_min_int(fz, smi);
-    n = rank_quality_cut(p, N, n, pf, ebuf, smi, cut_sh, acc_sh);
+    n = rank_quality_cut(rq, N, n, pf, ebuf, smi, cut_sh, acc_sh);
     // P3: apply_quality renormalises the kept values by np.sum over the array (zeros elsewhere); the support is
     // what stays > 0 (_rank_tokens' mask)
-    const bool filtered = p.rk_top_k > 0 || p.rk_top_p > 0.0 || p.rk_min_prob >= 0.0;
+    const bool filtered = rq.top_k > 0 || rq.top_p > 0.0 || rq.min_prob >= 0.0;
     double F = 1.0, S_trace = crypto ? tot : 0.0;
     if ((crypto || filtered) && n > 0) {
         const uint64_t kth = sk[n - 1];
@@ -2167,7 +2171,7 @@ __global__ __launch_bounds__(WIDE_THREADS) void wide_rank64_kernel(StepParams p,
     // P4: cap over the array's entries (a dict that went through apply_quality keeps only its positive entries)
     if (!crypto) {
         const int U = (p.rk_dict && filtered) ? n : N;
-        n = rank_cap(p, U, n, [&](int i) -> double { return filtered ? pf(i) / F : pf(i); }, sm64, smi);
+        n = rank_cap(rq, U, n, [&](int i) -> double { return filtered ? pf(i) / F : pf(i); }, sm64, smi);
     }
     // P5: selection / emission; the token of rank i is the id of its array position
     auto id_of = [&](int i) -> int32_t {

@@ -13,6 +13,11 @@ positions modulo ``n_positions`` -- the same logits while the context fits ``n_p
 fails beyond it).  With ``max_context`` (``lm/arithmetic.py:50-51,106-112``) the trimmed window's positions shift
 every token, so no cache applies: each step re-runs every stream's last ``max_context`` tokens from scratch
 (:class:`WindowedLM`, the batched GPT-2's native causal sequence forward), exactly the reference's computation.
+
+``encode_batch`` / ``encode_batch_states`` / ``decode_batch`` take one shared ``context`` and ``quality`` (every stream
+in lockstep on the contiguous cache), or -- with ``contexts=``, ``qualities=`` or ``slots=`` on the native GPT-2 -- one
+context and one quality per message in one slot-scheduled batch on the paged cache (``lm/slots.py``,
+``ns_rank_*_step_streams``), each message with the tokens and history of its own one-message call.
 """
 
 from __future__ import annotations
@@ -219,19 +224,118 @@ class HipRankLM:
             return self.lm
         return WindowedLM(self.lm, mc)
 
-    def encode_batch(self, bit_lists: Sequence[Sequence[int]], context: Sequence[int], *,
-                     quality: Mapping[str, object], max_steps: int = 1 << 16) -> List[List[int]]:
-        toks, states = self.encode_batch_states(bit_lists, context, quality=quality, max_steps=max_steps)
+    def encode_batch(self, bit_lists: Sequence[Sequence[int]], context: Optional[Sequence[int]] = None, *,
+                     contexts: Optional[Sequence[Sequence[int]]] = None,
+                     quality: Optional[Mapping[str, object]] = None,
+                     qualities: Optional[Sequence[Mapping[str, object]]] = None, slots: Optional[int] = None,
+                     graphs: Optional[bool] = None, max_steps: int = 1 << 16) -> List[List[int]]:
+        """:meth:`encode_batch_states` with every message's state queued on the provider, in message order."""
+        toks, states = self.encode_batch_states(bit_lists, context, contexts=contexts, quality=quality,
+                                                qualities=qualities, slots=slots, graphs=graphs, max_steps=max_steps)
         for st in states:
             self._encode_states.append(dict(st))
             self._decode_states.append(dict(st))
         return toks
 
-    def encode_batch_states(self, bit_lists: Sequence[Sequence[int]], context: Sequence[int], *,
-                            quality: Mapping[str, object], max_steps: int = 1 << 16):
-        """:meth:`encode_batch` returning ``(tokens, states)`` -- each stream's ``{"history", "residual_bits"}``
+    def encode_batch_states(self, bit_lists: Sequence[Sequence[int]], context: Optional[Sequence[int]] = None, *,
+                            contexts: Optional[Sequence[Sequence[int]]] = None,
+                            quality: Optional[Mapping[str, object]] = None,
+                            qualities: Optional[Sequence[Mapping[str, object]]] = None, slots: Optional[int] = None,
+                            graphs: Optional[bool] = None, max_steps: int = 1 << 16):
+        """Encode ``bit_lists``; returns ``(tokens, states)`` -- each message's ``{"history", "residual_bits"}``
         side channel -- without queueing the states on the provider (``codec.rank.encode_with_lm`` hands them
-        to the caller's ``state`` dict instead)."""
+        to the caller's ``state`` dict instead).
+
+        Give exactly one of ``context`` (shared) / ``contexts`` (one per message) and exactly one of ``quality`` /
+        ``qualities``.  With one shared context, one quality and no ``slots`` the streams run in lockstep on the
+        contiguous cache, as they always did.  With ``contexts=``, ``qualities=`` or ``slots=`` on the native GPT-2
+        the messages run through ``min(N, slots or max_batch)`` slots on the paged KV cache
+        (:class:`~neuralsteganography_amd.lm.slots.RankSlotEncoder`): every message with its own context (equal
+        contexts and common prefixes share pages; a shared ``context`` is that context N times) and its own
+        temperature and policy (one row of the rank quality table), with exactly the tokens and history of its own
+        one-message call.  A quality with ``max_context`` and a non-native LM fall back to one lockstep call per
+        distinct (context, quality).  ``last_schedule`` records the run."""
+        ctxs, quals = self._call_shape(len(bit_lists), context, contexts, quality, qualities)
+        if contexts is None and qualities is None and slots is None:
+            return self._encode_lockstep(bit_lists, context, quality, max_steps)
+        if not bit_lists:
+            return [], []
+        if not self._slot_path(quals):
+            res = self._by_group(ctxs, quals, lambda idx, c, q: list(zip(*self._encode_lockstep(
+                [bit_lists[i] for i in idx], c, q, max_steps))))
+            return [r[0] for r in res], [r[1] for r in res]
+        from ..coder import RankStreamQuality
+        from .slots import RankSlotEncoder
+
+        rows = RankStreamQuality.from_qualities(quals)
+        for b in bit_lists:
+            if len(b) % 8:
+                raise ConfigurationError("bit stream length must be a multiple of 8")
+        S = max(1, min(len(bit_lists), int(slots) if slots else self.max_batch))
+        enc = RankSlotEncoder(self, self._coder(S), [list(b) for b in bit_lists], [self._context(c) for c in ctxs],
+                              rows, slots=S, use_graph=graphs is None or bool(graphs), check_every=self.check_every,
+                              compact=self.slot_compaction, share=self.share_contexts,
+                              share_prefixes=self.share_prefixes)
+        toks, _ = enc.run()
+        self.last_schedule = self._schedule(enc, S)
+        states = [{"history": tuple(enc.consumed[i]), "residual_bits": len(b).to_bytes(8, "big")}
+                  for i, b in enumerate(bit_lists)]
+        return [list(t) for t in toks], states
+
+    # the slot loops' switches (as HipArithmeticLM's)
+    share_contexts = True    # equal contexts of a call share the context's KV pages
+    share_prefixes = True    # different contexts share the pages of a common prefix (fp16 pages)
+    slot_compaction = True   # compact the live slots once the queue is drained
+    check_every = 16         # steps between host checks of the slot loops
+
+    @staticmethod
+    def _call_shape(n: int, context, contexts, quality, qualities, states=None):
+        """Validate a batched call before any GPU work; returns one context and one quality per message."""
+        if (context is None) == (contexts is None):
+            raise ConfigurationError("give exactly one of context (shared) and contexts (one per message)")
+        if (quality is None) == (qualities is None):
+            raise ConfigurationError("give exactly one of quality (shared) and qualities (one per message)")
+        if contexts is not None and len(contexts) != n:
+            raise ConfigurationError(f"{len(contexts)} contexts for {n} messages")
+        if qualities is not None and len(qualities) != n:
+            raise ConfigurationError(f"{len(qualities)} qualities for {n} messages")
+        if states is not None and len(states) != n:
+            raise ConfigurationError(f"{len(states)} states for {n} messages")
+        ctxs = [list(c) for c in contexts] if contexts is not None else [list(context)] * n
+        quals = [dict(q or {}) for q in qualities] if qualities is not None else [dict(quality or {})] * n
+        return ctxs, quals
+
+    def _slot_path(self, quals) -> bool:
+        """Whether the call runs in the slot loops: the native GPT-2 and no ``max_context`` window."""
+        if not getattr(self.lm, "native", False) or getattr(self.lm, "prob_rows", False):
+            return False
+        return not any(_max_context(q) for q in quals)
+
+    @staticmethod
+    def _by_group(ctxs, quals, run):
+        """``run(indices, context, quality)`` -- one lockstep call, a result per index -- once per distinct
+        (context, quality), results back in message order."""
+        groups: Dict[tuple, List[int]] = {}
+        for i, (c, q) in enumerate(zip(ctxs, quals)):
+            groups.setdefault((tuple(c), tuple(sorted((k, repr(v)) for k, v in q.items()))), []).append(i)
+        out: List[object] = [None] * len(ctxs)
+        for idx in groups.values():
+            for i, r in zip(idx, run(idx, ctxs[idx[0]], quals[idx[0]])):
+                out[i] = r
+        return out
+
+    @staticmethod
+    def _schedule(run, S: int) -> Dict[str, int]:
+        sched = {"slots": S, "evictions": run.evictions, "compactions": run.compactions,
+                 "kv_pages_peak": run.kv_peak, "prefill_rows": run.prefill_rows,
+                 "prefill_groups": run.prefill_groups, "prefill_shared": run.prefill_shared, "quality_groups": 1}
+        if run.prefix_entries:
+            sched.update(prefix_rows_saved=run.prefix_rows_saved, prefix_entries=run.prefix_entries)
+        return sched
+
+    def _encode_lockstep(self, bit_lists, context, quality, max_steps: int = 1 << 16):
+        """One shared context and quality: every stream steps in lockstep on the contiguous cache until the slowest
+        finishes."""
         B = len(bit_lists)
         if B == 0:
             return [], []
@@ -271,8 +375,56 @@ class HipRankLM:
             states.append({"history": tuple(cons[i]), "residual_bits": (8 * len(payloads[i])).to_bytes(8, "big")})
         return toks, states
 
-    def decode_batch(self, token_lists: Sequence[Sequence[int]], context: Sequence[int], *,
-                     quality: Mapping[str, object], states: Optional[Sequence[CodecState]] = None) -> List[List[int]]:
+    def decode_batch(self, token_lists: Sequence[Sequence[int]], context: Optional[Sequence[int]] = None, *,
+                     contexts: Optional[Sequence[Sequence[int]]] = None,
+                     quality: Optional[Mapping[str, object]] = None,
+                     qualities: Optional[Sequence[Mapping[str, object]]] = None,
+                     states: Optional[Sequence[CodecState]] = None, slots: Optional[int] = None,
+                     graphs: Optional[bool] = None) -> List[List[int]]:
+        """Decode ``token_lists`` with one state per message (``states``, or the queued ones popped in message
+        order).  The arguments and the choice of path are those of :meth:`encode_batch_states`; the slot path is
+        :class:`~neuralsteganography_amd.lm.slots.RankSlotDecoder`, recorded in ``last_decode_schedule``."""
+        B = len(token_lists)
+        ctxs, quals = self._call_shape(B, context, contexts, quality, qualities, states)
+        if contexts is None and qualities is None and slots is None:
+            return self._decode_lockstep(token_lists, context, quality, states)
+        if B == 0:
+            return []
+        if states is None:
+            states = [self._decode_states.popleft() if self._decode_states else {} for _ in range(B)]
+        if not self._slot_path(quals):
+            return self._by_group(ctxs, quals, lambda idx, c, q: self._decode_lockstep(
+                [token_lists[i] for i in idx], c, q, [states[i] for i in idx]))
+        from ..codec.errors import DecodeDivergenceError
+        from ..coder import RankStreamQuality
+        from .slots import RankSlotDecoder
+
+        hist = [list(s.get("history") or ()) for s in states]
+        for i, (tl, hs) in enumerate(zip(token_lists, hist)):
+            if any(not 0 <= int(t) < self.vocab for t in tl):
+                raise DecodeDivergenceError(f"message {i}: token id outside [0, {self.vocab})")
+            if len(hs) < len(tl):
+                raise DecodeDivergenceError("Bit consumption history is required for decoding")
+        rows = RankStreamQuality.from_qualities(quals)
+        out: List[List[int]] = [[] for _ in range(B)]
+        if not any(len(t) for t in token_lists):
+            return out
+        S = max(1, min(B, int(slots) if slots else self.max_batch))
+        dec = RankSlotDecoder(self, self._coder(S), [list(t) for t in token_lists], hist,
+                              [self._context(c) for c in ctxs], rows, slots=S,
+                              use_graph=graphs is None or bool(graphs), check_every=self.check_every,
+                              compact=self.slot_compaction, share=self.share_contexts,
+                              share_prefixes=self.share_prefixes)
+        payloads, _ = dec.run()
+        self.last_decode_schedule = self._schedule(dec, dec.S)
+        for i, pl in enumerate(payloads):
+            nb = states[i].get("residual_bits")
+            if nb:
+                pl = pl[: int.from_bytes(bytes(nb), "big") // 8]
+            out[i] = _bytes_to_bits(pl)
+        return out
+
+    def _decode_lockstep(self, token_lists, context, quality, states=None) -> List[List[int]]:
         import torch
 
         B = len(token_lists)

@@ -32,6 +32,11 @@ With ``qualities`` (one coder quality per message, library 0.31) every slot also
 quality table (``ns_set_stream_quality``): an admission -- the first fill, a refill, a re-admission after an eviction,
 with or without per-message contexts -- writes the message's row together with its payload and fresh state, a
 compaction permutes the table with the other per-slot tensors, and the table is part of the graph's layout key.
+
+The rank coder (library 0.31.5) runs through the same loops: :class:`RankSlotEncoder` is :class:`SlotEncoder` over
+``coder.RankStreamEncodeSession`` and :class:`RankSlotDecoder` is :class:`SlotSampler`'s loop over
+``coder.RankStreamDecodeSession``, every slot with its message's row of the rank quality table
+(``ns_rank_stream_quality``: temperature and policy), given to ``ns_rank_*_step_streams`` with each step.
 """
 
 from __future__ import annotations
@@ -283,8 +288,7 @@ class SlotEncoder:
             first = lm.first_logits
         T0 = lm.kv.T0
         stride = max(1, (max_bits + 7) // 8)
-        sess = EncodeSession(self.ctx, self.bits[:S], max_tokens=budget, stats=self.stats, payload_stride=stride,
-                             quality=self._rows(range(S)))
+        sess = self._session(S, budget, stride)
         stop = _StopCheck(self.p, sess, self.stop_text) if self.stop_text is not None else None
         if per_ctx:
             sess.park_slots(np.arange(S))
@@ -340,8 +344,7 @@ class SlotEncoder:
                     if fin.size:
                         bad = fin[(flags[fin] & _lib.NS_ST_ERR_RANGE) != 0]
                         if bad.size:
-                            raise ArithmeticRangeError(
-                                f"streams {slot_msg[bad].tolist()[:8]} found no CDF bucket for the payload index")
+                            raise ArithmeticRangeError(self._range_error(slot_msg[bad].tolist()[:8]))
                         nt = f["ntokens"][fin]
                         if int(nt.max(initial=0)) > sess.hist.shape[1]:
                             raise RuntimeError("token history overflow")
@@ -358,6 +361,7 @@ class SlotEncoder:
                             tokens[m] = host[j, : int(nt[j])].tolist()
                             if self.stats:
                                 stats_out[m] = _stats_rows(acc[j:j + 1], f["bit_pos"][s:s + 1])[0]
+                        self._harvested(sess, fin, slot_msg[fin], nt, ev, side)
                         lm.kv.release(fin)
                         slot_msg[fin] = -1
                         admit_blocked = False
@@ -438,7 +442,7 @@ class SlotEncoder:
                     if pipelined:
                         pending = pin.take(sess.state)
                 key = _layout_key(logits, sess.state, sess.hist, sess.payload, lm.kv.table, lm.kv.lens,
-                                  sess.stats_acc, sess.qtable) + (lm.kv.version,)
+                                  sess.stats_acc, sess.qtable) + (lm.kv.version,) + self._key_extra(sess)
                 if self.use_graph:
                     if graph is None or key != gkey:
                         graph = None
@@ -466,6 +470,21 @@ class SlotEncoder:
     def _rows(self, msgs):
         """The quality rows of messages ``msgs`` (None without per-message qualities)."""
         return self.qual.take(list(msgs)) if self.qual is not None else None
+
+    # what a subclass with another coder session replaces (RankSlotEncoder)
+    def _session(self, S: int, budget: int, stride: int):
+        """The coder session of the run: the first S messages loaded (a per-context run parks them all first)."""
+        return EncodeSession(self.ctx, self.bits[:S], max_tokens=budget, stats=self.stats, payload_stride=stride,
+                             quality=self._rows(range(S)))
+
+    def _range_error(self, msgs) -> str:
+        return f"streams {msgs} found no CDF bucket for the payload index"
+
+    def _harvested(self, sess, fin, msgs, nt, ev, side) -> None:
+        """Finished slots ``fin`` (messages ``msgs``, ``nt`` tokens each) just handed their tokens over."""
+
+    def _key_extra(self, sess) -> tuple:
+        return ()
 
     def _admit(self, sess, logits, first, slots, msgs, slot_msg, last_pos, last_move, t):
         import torch
@@ -1085,8 +1104,6 @@ class SlotSampler:
     def run(self):
         import torch
 
-        from ..coder import SampleSession
-
         lm, S, N = self.lm, self.S, self.N
         Lmax = int(self.lengths.max())
         order = np.argsort(-self.lengths, kind="stable")  # longest first: the tail is short messages
@@ -1096,8 +1113,7 @@ class SlotSampler:
         logits = torch.zeros((S, lm.ld), device=lm.device, dtype=lm.logits_dtype)
         dev = logits.device
         # every slot starts parked (length 0) on a valid quality row
-        sess = SampleSession(self.ctx, S, max_tokens=max(1, min(int(budget), Lmax)), stats=self.stats,
-                             quality=self.qual.take([0] * S), seeds=[0] * S, gids=[0] * S, lengths=[0] * S)
+        sess = self._session(S, int(budget), Lmax)
         stop = torch.zeros(S, dtype=torch.int32, device=dev)
         ctx_host = np.zeros(S, dtype=np.int64)
         len_host = np.zeros(S, dtype=np.int64)
@@ -1136,12 +1152,7 @@ class SlotSampler:
                     fin = np.nonzero(done)[0]
                     if fin.size:
                         nl = len_host[fin]
-                        if ev is not None:
-                            host = _rows_after(ev, side, sess.hist, fin, int(nl.max())).numpy()
-                            acc = _rows_after(ev, side, sess.stats_acc, fin).numpy() if self.stats else None
-                            got = [host[j, : int(nl[j])].tolist() for j in range(fin.size)]
-                        else:
-                            got, acc = sess.harvest(fin, nl)
+                        got, acc = self._harvest(sess, fin, nl, ev, side, slot_msg[fin])
                         for j, s in enumerate(fin.tolist()):
                             m = int(slot_msg[s])
                             tokens[m] = got[j]
@@ -1206,8 +1217,7 @@ class SlotSampler:
                         ev_now = torch.cuda.Event()
                         ev_now.record()
                         pending = (ev_now, slot_msg.copy(), lm.kv.lens_host - ctx_host)
-                key = _layout_key(logits, sess.state, sess.hist, sess.out_token, sess.stats_acc, sess.qtable,
-                                  sess.draws, stop, lm.kv.table, lm.kv.lens) + (lm.kv.version,)
+                key = self._key(sess) + _layout_key(logits, stop, lm.kv.table, lm.kv.lens) + (lm.kv.version,)
                 if self.use_graph:
                     if graph is None or key != gkey:
                         graph = None
@@ -1227,6 +1237,29 @@ class SlotSampler:
             del graph
         self.kv_peak = lm.kv.peak
         return tokens, (stats_out if self.stats else None)
+
+    # what a subclass with another coder session replaces (RankSlotDecoder)
+    def _session(self, S: int, budget: int, Lmax: int):
+        """The coder session of the run: every slot parked (length 0) on a valid quality row."""
+        from ..coder import SampleSession
+
+        return SampleSession(self.ctx, S, max_tokens=max(1, min(int(budget), Lmax)), stats=self.stats,
+                             quality=self.qual.take([0] * S), seeds=[0] * S, gids=[0] * S, lengths=[0] * S)
+
+    def _harvest(self, sess, fin, nl, ev, side, msgs):
+        """``(results, accumulators or None)`` of the finished slots ``fin`` (messages ``msgs``, lengths ``nl``); with
+        ``ev`` (the pipelined check) gathered on the ``side`` stream once the event has passed."""
+        if ev is not None:
+            host = _rows_after(ev, side, sess.hist, fin, int(nl.max())).numpy()
+            acc = _rows_after(ev, side, sess.stats_acc, fin).numpy() if self.stats else None
+            return [host[j, : int(nl[j])].tolist() for j in range(fin.size)], acc
+        return sess.harvest(fin, nl)
+
+    def _key(self, sess) -> tuple:
+        return _layout_key(sess.state, sess.hist, sess.out_token, sess.stats_acc, sess.qtable, sess.draws)
+
+    def _load(self, sess, slots, msgs, nl) -> None:
+        sess.load_slots(slots, self.qual.take(msgs), [self.seeds[m] for m in msgs], [self.gids[m] for m in msgs], nl)
 
     def _admit_contexts(self, sess, logits, stop, slots, msgs, slot_msg, len_host, ctx_host):
         """Admit ``msgs`` into ``slots``: pages for each context and the message's first positions, one ragged prefill
@@ -1252,7 +1285,7 @@ class SlotSampler:
         self.prefill_rows += lm.last_prefill["rows"]
         self.prefill_groups += lm.last_prefill["groups"]
         self.prefill_shared += lm.last_prefill["shared"]
-        sess.load_slots(slots, self.qual.take(msgs), [self.seeds[m] for m in msgs], [self.gids[m] for m in msgs], nl)
+        self._load(sess, slots, msgs, nl)
         idx = torch.as_tensor(slots, device=logits.device)
         # the attention is skipped once the cache length reaches context + length - 1: the logits after the last
         # drawn token are never read
@@ -1262,3 +1295,87 @@ class SlotSampler:
         ctx_host[slots] = tl
         len_host[slots] = nl
         return back
+
+
+class RankSlotEncoder(SlotEncoder):
+    """:class:`SlotEncoder` over the rank coder (``coder.RankStreamEncodeSession``, ``ns_rank_encode_step_streams``):
+    every message has its own context and its own row of the rank quality table (temperature and policy).  The loop --
+    admission, shared pages, the pipelined check, graph capture, eviction, compaction -- is the parent's; a finished
+    slot hands over its consumption history (the reference's ``state["history"]``) with its tokens.  The step depends
+    on nothing but the stream's own logits, payload and row, so a message gives the tokens of its one-message call in
+    any slot, and an evicted message gives them again."""
+
+    def __init__(self, provider, ctx, bit_lists, contexts, qualities, *, slots: int, use_graph: bool,
+                 check_every: int = 16, compact: bool = True, share: bool = True, share_prefixes: bool = True):
+        max_bits = max(len(b) for b in bit_lists)
+        # a rank stream consumes at least one bit per token: it never stalls and never exceeds its bit count
+        super().__init__(provider, ctx, bit_lists, None, slots=slots, finish=False, stop_text=None, stats=False,
+                         check_every=check_every, stall_steps=1 << 30, hard_cap=max_bits + 64, use_graph=use_graph,
+                         compact=compact, contexts=contexts, share=share, qualities=qualities,
+                         share_prefixes=share_prefixes)
+        self.consumed: List[Optional[List[int]]] = [None] * self.N
+
+    def _session(self, S: int, budget: int, stride: int):
+        from ..coder import RankStreamEncodeSession
+
+        return RankStreamEncodeSession(self.ctx, S, payload_stride=stride, max_tokens=budget)
+
+    def _range_error(self, msgs) -> str:
+        return f"messages {msgs}: language model distribution provides no capacity"
+
+    def _harvested(self, sess, fin, msgs, nt, ev, side) -> None:
+        import torch
+
+        ncol = max(1, int(nt.max()))
+        if ev is not None:
+            host = _rows_after(ev, side, sess.cons, fin, ncol).numpy()
+        else:
+            host = sess.cons[torch.as_tensor(fin, device=sess.cons.device), :ncol].cpu().numpy()
+        for j, m in enumerate(msgs.tolist()):
+            self.consumed[int(m)] = host[j, : int(nt[j])].tolist()
+
+    def _key_extra(self, sess) -> tuple:
+        return _layout_key(sess.cons, sess.nbits, sess.out_token)
+
+
+class RankSlotDecoder(SlotSampler):
+    """:class:`SlotSampler`'s loop over the rank decoder (``coder.RankStreamDecodeSession``,
+    ``ns_rank_decode_step_streams``): a message's end is known on the host from its token count, a slot past its last
+    token is inactive on the device, and every message has its own context, consumption history and row of the rank
+    quality table.  ``run()`` returns each message's decoded bytes."""
+
+    def __init__(self, provider, ctx, token_lists, histories, contexts, qualities, *, slots: int, use_graph: bool,
+                 check_every: int = 16, compact: bool = True, share: bool = True, share_prefixes: bool = True):
+        n = len(token_lists)
+        super().__init__(provider, ctx, contexts, [len(t) for t in token_lists], qualities, [0] * n, [0] * n,
+                         slots=slots, use_graph=use_graph, stats=False, check_every=check_every, compact=compact,
+                         share=share, share_prefixes=share_prefixes)
+        self.lists = token_lists
+        self.hists = [list(h)[: len(t)] for t, h in zip(token_lists, histories)]
+
+    def _session(self, S: int, budget: int, Lmax: int):
+        from ..coder import RankStreamDecodeSession
+
+        return RankStreamDecodeSession(self.ctx, S, max_tokens=Lmax,
+                                       max_bits=max((sum(h) for h in self.hists), default=0))
+
+    def _harvest(self, sess, fin, nl, ev, side, msgs):
+        from ..codec.errors import DecodeDivergenceError
+        from ..coder import RankStreamDecodeSession
+
+        if ev is not None:
+            st, ob = _rows_after(ev, side, sess.state, fin), _rows_after(ev, side, sess.out_bits, fin)
+            flags = _state_fields(st)["flags"]
+            got = RankStreamDecodeSession.payloads_of(st, ob)
+        else:
+            got, flags = sess.harvest(fin)
+        bad = msgs[(flags & _lib.NS_ST_ERR_DIVERGE) != 0]
+        if bad.size:
+            raise DecodeDivergenceError(f"messages {bad.tolist()[:8]}: token not present in distribution")
+        return got, None
+
+    def _key(self, sess) -> tuple:
+        return _layout_key(sess.state, sess.tokmat, sess.keepmat, sess.nlen, sess.out_bits, sess.qtable)
+
+    def _load(self, sess, slots, msgs, nl) -> None:
+        sess.load_slots(slots, [self.lists[m] for m in msgs], [self.hists[m] for m in msgs], self.qual.take(msgs))

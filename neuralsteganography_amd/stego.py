@@ -96,7 +96,8 @@ def packet_prefix(data: bytes) -> bytes:
 
 def _qkw(entry, quality) -> Dict[str, Any]:
     """The quality keyword of a batched provider entry: ``quality`` (one dict), or ``qualities`` (a list, one per
-    stream) for a provider that takes it; None when the entry cannot take the list (the caller goes per stream)."""
+    stream) for a provider that takes it (the arithmetic and the rank provider both do); None when the entry cannot
+    take the list (the caller goes per stream)."""
     if not isinstance(quality, list):
         return {"quality": quality}
     if all(q == quality[0] for q in quality):
@@ -144,8 +145,9 @@ def _decode_streams(lm, spans: List[List[int]], context: List[int], quality, chu
 
 
 def _encode_streams_each(lm, bit_lists: List[List[int]], contexts: List[List[int]], quality) -> List[List[int]]:
-    """``_encode_streams`` with one context per stream (``seed_texts``).  A provider whose ``encode_batch`` takes
-    one shared context only (the rank coder) is driven per packet, in order, as a provider without one is."""
+    """``_encode_streams`` with one context per stream (``seed_texts``): one ``encode_batch(contexts=...)`` call for a
+    provider that takes it (the arithmetic and the rank provider both do).  A provider whose ``encode_batch`` takes one
+    shared context only is driven per packet, in order, as a provider without one is."""
     kw = _qkw(getattr(lm, "encode_batch", None), quality) if _takes_contexts(getattr(lm, "encode_batch", None)) else None
     if kw is not None:
         return lm.encode_batch(bit_lists, contexts=contexts, **kw)
