@@ -1,7 +1,9 @@
 """GPU: ``decode_batch(..., chunk=C)`` / ``stego_decode_batch(..., chunk=C)`` -- a slot's next C cover tokens through
 the LM in one forward, the coder token by token -- must decode the SAME BITS as ``chunk=1`` and give the payloads
 back, through slot refill, compaction, per-message contexts (equal ones and a shared 64-token prefix), per-message
-qualities, fp8 pages, alone after a batched encode, and report a diverging cover for the same message.
+qualities, fp8 pages, alone after a batched encode, and report a diverging cover for the same message.  On a capped
+page pool the decoder (``chunk`` 1 and 5) evicts and re-decodes messages to the same bits, and raises
+``KVCapacityError`` for a message that cannot fit alone.
 
 The tiny model of tests/test_gpu_step_chunk.py (n_embd 128, 2 heads, 2 layers, n_positions 64, vocab 512).
 """
@@ -13,6 +15,8 @@ torch = pytest.importorskip("torch")
 
 from neuralsteganography_amd import synthetic  # noqa: E402
 from neuralsteganography_amd.codec.errors import DecodeDivergenceError  # noqa: E402
+from neuralsteganography_amd.exceptions import KVCapacityError  # noqa: E402
+from neuralsteganography_amd.lm.kvpages import PAGE_ROWS  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -176,3 +180,65 @@ def test_chunk_is_validated():
             lm.decode_batch([[1, 2, 3]], _context(), quality=Q, chunk=2)
     finally:
         lm.lm.window = 0
+
+
+def _capped(cap_pages):
+    """A fresh provider whose page pool never holds more than ``cap_pages`` pages."""
+    lm = _provider()
+    lm.lm.kv_segment_pages = 1  # a page-exact budget
+    pool = lm.lm.page_pool()
+    pool.budget_bytes = lambda: (cap_pages - pool.total) * pool.page_bytes
+    return lm, pool
+
+
+@pytest.fixture(scope="module", params=[False, True], ids=["one_context", "contexts"])
+def evictable(request):
+    """8 messages of 24-40 bytes at Q2 (at most log2(40) bits a token: every cover is longer than one page), encoded
+    and decoded on an uncapped pool, and a pool cap under which they cannot all be live at once.  A message's pages at
+    its peak are ``ceil(rows / 32)``, its rows the cover's tokens and, with per-message contexts, its context's (the
+    one shared context lies outside the pool).  The cap is two pages more than the longest message needs alone: the
+    first admission then takes ``cap - 1`` messages at one page each (a context of at most 12 tokens and the first
+    20 positions), and they all need their second page at the same check."""
+    lm = _provider()
+    bits = _bits([40, 24, 36, 28, 32, 26, 38, 30], seed0=2100)
+    if request.param:
+        rng = np.random.default_rng(23)
+        kw = {"contexts": [rng.integers(0, V - 1, size=int(n)).tolist() for n in rng.integers(3, 13, size=len(bits))]}
+        own = [len(c) for c in kw["contexts"]]
+    else:
+        kw, own = {"context": _context()}, [0] * len(bits)
+    covers = lm.encode_batch(bits, quality=Q2, **kw)
+    ref = lm.decode_batch(covers, quality=Q2, **kw)
+    _check(ref, bits)
+    need = [-(-(t + len(c)) // PAGE_ROWS) for t, c in zip(own, covers)]
+    cap_pages = max(need) + 2
+    assert max(need) <= cap_pages < sum(need), (need, cap_pages)
+    return covers, kw, ref, cap_pages
+
+
+@pytest.mark.parametrize("C", [1, 5])
+def test_decoder_evicts_when_the_pool_is_small_and_gives_the_same_bits(evictable, C):
+    covers, kw, ref, cap_pages = evictable
+    lm, pool = _capped(cap_pages)
+    out = lm.decode_batch(covers, quality=Q2, chunk=C, **kw)
+    sched = dict(lm.last_decode_schedule)
+    print(f"cap_pages={cap_pages} chunk={C} {sorted(kw)} schedule={sched} pool={pool.free_pages}/{pool.total}")
+    assert out == ref
+    assert sched["evictions"] > 0, sched
+    assert pool.total <= cap_pages
+    assert pool.free_pages == pool.total  # every page came back
+
+
+@pytest.mark.parametrize("C", [1, 5])
+def test_decoder_kv_capacity_error_not_torch_oom(C):
+    """One cover of more than 64 tokens on a pool of 2 pages (64 positions): ``KVCapacityError``, and the pool never
+    grows past its cap.  The failed message still holds its two pages when the error leaves the loop (0 of 2 free,
+    measured at both chunks); the next call's ``begin_slots`` frees them."""
+    context = _context()
+    covers = _provider().encode_batch(_bits([60], seed0=2300), context, quality=Q2)
+    assert len(covers[0]) > 2 * PAGE_ROWS
+    lm, pool = _capped(2)
+    with pytest.raises(KVCapacityError):
+        lm.decode_batch(covers, context, quality=Q2, chunk=C)
+    print(f"chunk={C} pool={pool.free_pages}/{pool.total}")
+    assert pool.total <= 2
