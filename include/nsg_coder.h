@@ -308,6 +308,39 @@ int ns_sample_step_streams(ns_ctx* ctx, const void* d_logits, int64_t ld, int B,
                            int32_t* d_token_hist, int64_t hist_stride, const int32_t* banned, int nbanned,
                            double* d_stats, ns_step_trace* d_trace, uint32_t step_flags, void* hip_stream);
 
+/* The decode step with every per-stream value taken from DEVICE tables given to the call itself (nothing is
+ * registered on the context, and nothing of the step depends on the row index b): d_quality[b] is stream b's
+ * ns_stream_quality row, filled by ns_stream_quality_fill for this k_max; d_tokens is [B, tok_stride] int32, the
+ * received tokens of stream b from b*tok_stride on; d_length[b] int32 their count (<= tok_stride and
+ * <= counts_stride; a token index outside either row parks the stream).  The stream's token index is its own
+ * state's ntokens (0 after ns_init_state or a host reset at admission), which every successful step advances as
+ * ns_decode_step does:
+ *   - the step reads token t = ntokens from d_tokens[b*tok_stride + t]; it is the stream's LAST token (all
+ *     `precision` bits of the new bottom are emitted) iff t == d_length[b] - 1;
+ *   - after a successful step the stream's new bit_pos is stored at d_counts[b*counts_stride + t] (int64,
+ *     [B, counts_stride]: the bit-count history of the stream) and the consumed token at d_out_token[b] (the LM's
+ *     next input); both by the lane that writes the state;
+ *   - PARKED: a stream with ntokens >= d_length[b], or with NS_ST_DONE set, is skipped -- its state, bits, counts,
+ *     out token, trace and export stay as they are -- so a loop may run past a stream's end without a host check;
+ *   - divergence is exactly the contract documented at ns_set_rank_export: state and bits untouched, flags |=
+ *     NS_ST_ERR_DIVERGE | NS_ST_DONE, the ranked ids exported while an export is registered, no count and no out
+ *     token written for that token; the stream stays parked until the host clears both flags (and, to continue,
+ *     replaces the token).  NS_ST_ERR_RANGE as in ns_decode_step.
+ * The bits and states are those ns_decode_step emits for the same stream with the same (temp, topk, precision): it
+ * is the same kernel code reading its token, last and active values through the tables.  Every host decision --
+ * single-pass or wide, the rank-slot bucket, the split or wave-per-stream form, the sample -- follows k_max alone,
+ * so a captured step stays valid whatever the rows hold; a row's K may be anything in [1, k_max].  d_out_bits,
+ * out_stride, banned, d_trace and step_flags are those of ns_decode_step.  NS_ERR_CONFIG for a null context, a null
+ * or misaligned table (quality and counts 8 bytes, the int32 arrays 4), k_max < 1, tok_stride < 1,
+ * counts_stride < 1, a NS_DTYPE_F64 context and a registered quality table (as ns_sample_step_streams);
+ * NS_ERR_UNSUPPORTED for min(k_max, valid ids) > ns_max_topk(dtype) on a context created without the wide-path
+ * buffers (as ns_decode_step). */
+int ns_decode_step_streams(ns_ctx* ctx, const void* d_logits, int64_t ld, int B, const ns_stream_quality* d_quality,
+                           int k_max, const int32_t* d_tokens, int64_t tok_stride, const int32_t* d_length,
+                           ns_stream_state* d_state, uint8_t* d_out_bits, int64_t out_stride, int64_t* d_counts,
+                           int64_t counts_stride, int32_t* d_out_token, const int32_t* banned, int nbanned,
+                           ns_step_trace* d_trace, uint32_t step_flags, void* hip_stream);
+
 /* Per-stream quality row of the rank coder: everything one stream's rank step derives from (temp,
  * ns_rank_quality).  One row per stream in DEVICE memory, written by the caller (no kernel writes the table).  The
  * layout is fixed: 48 bytes, 8-byte aligned, fields at the offsets below. */

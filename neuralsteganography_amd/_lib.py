@@ -28,6 +28,7 @@ NS_MAX_BANNED = 8
 EXPORTS = ("ns_create", "ns_destroy", "ns_last_error", "ns_version", "ns_max_topk", "ns_set_split_max_batch",
            "ns_init_state",
            "ns_encode_step", "ns_decode_step", "ns_set_sentence_end", "ns_set_stats", "ns_sample_step", "ns_sample_step_streams",
+           "ns_decode_step_streams",
            "ns_set_rank_export",
            "ns_rank_encode_step", "ns_set_rank_rows", "ns_rank_decode_step", "ns_token_probs",
            "ns_rank_stream_quality_fill", "ns_rank_encode_step_streams", "ns_rank_decode_step_streams",
@@ -180,6 +181,10 @@ def lib() -> ctypes.CDLL:
     L.ns_sample_step_streams.restype = ctypes.c_int
     L.ns_sample_step_streams.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int, vp, vp, ctypes.c_int, vp, vp, vp,
                                          ctypes.c_int64, i32p, ctypes.c_int, vp, vp, ctypes.c_uint32, vp]
+    L.ns_decode_step_streams.restype = ctypes.c_int
+    L.ns_decode_step_streams.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int64, vp,
+                                         vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, i32p, ctypes.c_int, vp,
+                                         ctypes.c_uint32, vp]
     L.ns_read_counters.restype = ctypes.c_int
     L.ns_read_counters.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.ns_score_rows.restype = ctypes.c_int

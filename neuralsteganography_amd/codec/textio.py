@@ -52,18 +52,20 @@ def spans_to_text(spans: Sequence[Sequence[int]], seed_ids: Sequence[int], tok) 
 
 
 def text_to_spans(text: str, seed_ids: Sequence[int], tok, *, lm=None, quality=None,
-                  seed_text: Optional[str] = None) -> List[List[int]]:
+                  seed_text: Optional[str] = None, slots: Optional[int] = None) -> List[List[int]]:
     """``textio.py:58-63`` -- a ``NotImplementedError`` placeholder in the reference (span boundaries are not
     in the text).  Given the provider (``lm``), the quality the cover was made with and its ``seed_text``, the
     spans are recovered by decoding (:func:`neuralsteganography_amd.cover.texts_to_spans`).  Without ``lm``
-    the reference's behaviour is kept (``cover_reveal`` then reads a JSON spans payload)."""
+    the reference's behaviour is kept (``cover_reveal`` then reads a JSON spans payload).  ``slots`` is passed on
+    (the slot-scheduled search of a provider with ``reveal_spans``)."""
     if lm is None:
         raise NotImplementedError("text_to_spans is not yet implemented; provide spans JSON payloads for decoding")
     from ..cover import texts_to_spans
 
     if seed_text is None:
         seed_text = _need(tok).decode([int(i) for i in seed_ids])
-    return texts_to_spans([text], seed_text=seed_text, lm=lm, quality=quality)[0]
+    skw = {} if slots is None else {"slots": slots}
+    return texts_to_spans([text], seed_text=seed_text, lm=lm, quality=quality, **skw)[0]
 
 
 __all__ = ["seed_to_ids", "spans_to_text", "text_to_spans"]

@@ -944,6 +944,152 @@ class StreamingDecodeSession:
         return _bit_rows_to_lists(self.out_bits, f["bit_pos"])
 
 
+class DecodeStreamsSession:
+    """S slots of the arithmetic decoder with one quality row and one token row each (``ns_decode_step_streams``).
+
+    A slot holds its stream's received tokens; a step decodes, for every slot, the token at the slot's own index --
+    the stream's ``ntokens`` -- and stores the stream's bit count after that token in ``counts`` (the bit-count
+    history a span search needs).  A slot past its last token, or flagged ``NS_ST_DONE`` (a divergence: state and bits
+    untouched, its ranked ids in ``ranked``), is parked: nothing of it is written, so the loop may run steps without a
+    host check.  Every buffer is sized at construction from ``max_tokens`` and ``max_precision`` (the call's largest):
+    :meth:`step` reads nothing back, grows nothing and launches with fixed pointers, so a graph can replay it.  Every
+    slot starts parked on a valid row."""
+
+    def __init__(self, ctx: CoderContext, S: int, *, max_tokens: int, k_max: Optional[int] = None,
+                 max_precision: Optional[int] = None, rank_export: bool = True):
+        torch = _torch()
+        self.ctx, self.B = ctx, int(S)
+        if self.B < 1 or self.B > ctx.max_batch:
+            raise ConfigurationError(f"batch {self.B} outside [1, {ctx.max_batch}]")
+        if ctx.params.dtype == "f64":
+            raise ConfigurationError("provider probability rows have no arithmetic decode step")
+        self.k_max = int(k_max) if k_max is not None else int(ctx.params.topk)
+        if self.k_max < 1 or self.k_max > ctx.params.topk:
+            raise ConfigurationError("the coder context's topk must cover the session's k_max")
+        self.P = int(max_precision) if max_precision is not None else int(ctx.params.precision)
+        if not 1 <= self.P <= 60:
+            raise ConfigurationError("precision must be within [1, 60]")
+        dev = torch.device("cuda", ctx.device)
+        self.T = max(1, int(max_tokens))
+        self.tokmat = torch.zeros((self.B, self.T), dtype=torch.int32, device=dev)
+        self.nlen = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        self.counts = torch.zeros((self.B, self.T), dtype=torch.int64, device=dev)
+        self.out_token = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        # a token emits at most `precision` bits (the last one exactly that many)
+        self.out_stride = int((self.T * self.P + self.P + 7) // 8 + 8)
+        self.out_bits = torch.zeros((self.B, self.out_stride), dtype=torch.uint8, device=dev)
+        p = ctx.params
+        filler = StreamQuality([CoderParams(vocab=p.vocab, precision=self.P, temp=1.0, topk=1, dtype=p.dtype,
+                                            banned=p.banned)], k_max=self.k_max)
+        self.qtable = filler.table(dev).expand(self.B, 4).contiguous()
+        self.state = filler.init_rows(dev).expand(self.B, 4).contiguous()
+        self.rank_stride = int(min(self.k_max, ctx.K)) + 1
+        self.ranked = torch.full((self.B, self.rank_stride), -1, dtype=torch.int32, device=dev) if rank_export \
+            else None
+        self.trace = None
+        self.steps = 0
+
+    def enable_trace(self):
+        self.trace = _state_tensor(self.B, self.state.device)
+        return self.trace
+
+    def step(self, logits, *, force_exact: bool = False):
+        """One decode step for every slot; returns the out-token buffer ([B] int32: the token each stream consumed,
+        the LM's next input; a parked stream keeps its last value)."""
+        _check_logits(self.ctx, self.B, logits)
+        L = _lib.lib()
+        if self.ranked is not None:
+            self.ctx.check(L.ns_set_rank_export(self.ctx._h, _ptr(self.ranked), self.rank_stride), "ns_set_rank_export")
+        rc = L.ns_decode_step_streams(
+            self.ctx._h, _ptr(logits), logits.stride(0), self.B, _ptr(self.qtable), int(self.k_max), _ptr(self.tokmat),
+            self.T, _ptr(self.nlen), _ptr(self.state), _ptr(self.out_bits), self.out_stride, _ptr(self.counts), self.T,
+            _ptr(self.out_token), self.ctx._banned, self.ctx._nbanned, _ptr(self.trace),
+            _lib.NS_STEP_FORCE_EXACT_SUM if force_exact else 0, _stream_handle())
+        if self.ranked is not None:
+            L.ns_set_rank_export(self.ctx._h, ctypes.c_void_p(0), 0)
+        self.ctx.check(rc, "ns_decode_step_streams")
+        self.steps += 1
+        return self.out_token
+
+    # ---------------------------------------------------------------- slots (lm/slots.py: refill, compaction)
+    def load_slots(self, slots: Sequence[int], token_lists: Sequence[Sequence[int]], quality: StreamQuality) -> None:
+        """Start new streams in ``slots``: their tokens and count, their quality row, a fresh state (``ntokens`` 0,
+        ``hi = 2^precision`` of the row) and zeroed output bytes and counts."""
+        torch = _torch()
+        n = len(slots)
+        if n == 0:
+            return
+        if quality is None or len(quality) != n or len(token_lists) != n or quality.k_max != self.k_max:
+            raise ConfigurationError("load_slots: one token list and one quality row per slot, filled for the "
+                                     "session's k_max")
+        if quality.max_precision > self.P:
+            raise ConfigurationError("load_slots: a row's precision exceeds the one the session was sized for")
+        tok = np.zeros((n, self.T), dtype=np.int32)
+        nl = np.zeros(n, dtype=np.int32)
+        for i, tl in enumerate(token_lists):
+            k = len(tl)
+            if k > self.T:
+                raise ConfigurationError("stream longer than the session was sized for")
+            tok[i, :k] = np.asarray(tl, dtype=np.int32)
+            nl[i] = k
+        dev = self.state.device
+        idx = torch.as_tensor(np.asarray(slots, dtype=np.int64), device=dev)
+        self.tokmat[idx] = torch.from_numpy(tok).to(dev)
+        self.nlen[idx] = torch.from_numpy(nl).to(dev)
+        self.qtable[idx] = quality.table(dev)
+        self.state[idx] = quality.init_rows(dev)
+        self.out_bits[idx] = 0
+        self.counts[idx] = 0
+
+    def park_slots(self, slots: Sequence[int]) -> None:
+        """Park ``slots`` (token count 0): the step writes nothing for them."""
+        if len(slots) == 0:
+            return
+        torch = _torch()
+        idx = torch.as_tensor(np.asarray(slots, dtype=np.int64), device=self.state.device)
+        self.nlen[idx] = 0
+
+    def compact(self, keep: Sequence[int]) -> None:
+        """Keep rows ``keep`` (in that order) of every per-stream buffer: the session now has len(keep) streams."""
+        torch = _torch()
+        idx = torch.as_tensor(np.asarray(keep, dtype=np.int64), device=self.state.device)
+        for name in ("tokmat", "nlen", "counts", "out_token", "out_bits", "qtable", "state", "ranked", "trace"):
+            t = getattr(self, name)
+            if t is not None:
+                setattr(self, name, t.index_select(0, idx).contiguous())
+        self.B = len(keep)
+
+    def clear(self, slots: Sequence[int], tokens: Optional[Sequence[int]] = None) -> None:
+        """Re-arm diverged ``slots``: drop their divergence / done flags (state and bits were left untouched) and,
+        with ``tokens``, replace the token each of them diverged on."""
+        if len(slots) == 0:
+            return
+        torch = _torch()
+        dev = self.state.device
+        idx = torch.as_tensor(np.asarray(slots, dtype=np.int64), device=dev)
+        w = self.state.view(torch.int32)
+        w[idx, 7] = w[idx, 7] & ~(_lib.NS_ST_ERR_DIVERGE | _lib.NS_ST_DONE)
+        if tokens is not None:
+            at = w[idx, 6].long().clamp(0, self.T - 1)
+            self.tokmat[idx, at] = torch.as_tensor(np.asarray(tokens, dtype=np.int32), device=dev)
+
+    def harvest(self, slots: Sequence[int]):
+        """``(bits, counts, flags, ntokens)`` of ``slots``: per slot the decoded bit list (``bit_pos`` bits), the bit
+        count after each of its ``ntokens`` decoded tokens, its state flags and ``ntokens``."""
+        torch = _torch()
+        idx = torch.as_tensor(np.asarray(slots, dtype=np.int64), device=self.state.device)
+        f = _state_fields(self.state.index_select(0, idx))
+        nt = np.minimum(f["ntokens"].astype(np.int64), self.T)
+        bits = _bit_rows_to_lists(self.out_bits.index_select(0, idx), f["bit_pos"])
+        counts = _rows_to_lists(self.counts.index_select(0, idx), nt)
+        return bits, counts, f["flags"].copy(), nt
+
+    def ranked_ids(self, b: int) -> List[int]:
+        row = self.ranked[b].cpu().numpy()
+        end = np.nonzero(row < 0)[0]
+        return row[: int(end[0]) if end.size else row.size].astype(np.int64).tolist()
+
+
 def rank_quality(quality) -> "_lib.NsRankQuality":
     """src codec quality (``lm/arithmetic.py:77-95`` ``_normalise_quality``: topk/top_k, top_p, min_prob,
     cap_per_token_bits / cap_bits_per_token) -> ``ns_rank_quality``."""

@@ -336,39 +336,49 @@ def _cover_ids(text: str, seed_text: str, seed_ids: List[int], tok) -> Optional[
     return None
 
 
-def texts_to_spans(texts: Sequence[str], *, seed_text: Optional[str] = None,
-                   seed_texts: Optional[Sequence[str]] = None, lm,
-                   quality: Optional[Mapping[str, object]] = None) -> List[List[List[int]]]:
-    """Recover the token spans of many cover texts (the inverse of ``spans_to_text``, which the reference leaves
-    unimplemented, ``codec/textio.py:58-63``).  The text is re-tokenised, the seed's ids are stripped, and the
-    spans are found one per round: every cover's next span is decoded as one stream of a lockstep batch, the
-    packet completes at a known token and the span ends there or, with ``finish_sent``, at the following
-    sentence end.  A text that re-tokenises differently from the emitted ids (GPT-2 BPE merges, also across
-    span boundaries) is repaired while decoding with the reference's heuristics (``code_base/arithmetic.py:
-    233-242,300-342``, the provider's ``decode_counted_repair``): the spans are the repaired ids.
+def _quality_key(q: Mapping[str, Any]) -> str:
+    return repr(sorted(((str(k), v) for k, v in q.items())))
 
-    Exactly one of ``seed_text`` (shared) and ``seed_texts`` (one per text) is given.  With ``seed_texts`` every
-    text is stripped of its own seed and decoded after its own context: one lockstep batch with one context per
-    stream on a provider whose counted decodes take ``contexts=``, one batch per distinct context otherwise."""
+
+def _text_qualities(quality, qualities, n: int) -> Optional[List[Dict[str, Any]]]:
+    """One merged quality per text for ``qualities`` (None without them); at most one of the two is given."""
+    if qualities is None:
+        return None
+    if quality is not None:
+        raise ConfigurationError("give exactly one of quality (shared) and qualities (one per text)")
+    qs = [normalise_quality(q) for q in qualities]
+    if len(qs) != n:
+        raise ConfigurationError(f"{len(qs)} qualities for {n} texts")
+    return qs
+
+
+def _cover_rests(texts: Sequence[str], seeds: Sequence[str], tok) -> List[List[int]]:
+    """Every cover's token ids after its own seed (``_cover_ids``, double newlines split back)."""
     from .codec.errors import DecodeDivergenceError
-    from .lm.mock import MockLM
-    from .stego import _quality_args, _takes_contexts
 
-    tok = _tokenizer_of(lm)
-    seed_text, seeds = _one_or_many_seeds(seed_text, seed_texts, len(texts))
-    if seeds is None:
-        seeds = [seed_text] * len(texts)
     seed_ids = {s: seed_to_ids(s, tok) for s in set(seeds)}
-    contexts = {s: list(lm.encode_seed(s)) for s in set(seeds)}
-    q = _quality_args(quality)
-    finish = bool(q.get("finish_sent")) and hasattr(lm, "sentence_end_table")
-    sent_end = lm.sentence_end_table() if finish else None
     rest: List[List[int]] = []
     for i, text in enumerate(texts):
         ids = _cover_ids(text, seeds[i], seed_ids[seeds[i]], tok)
         if ids is None:
             raise DecodeDivergenceError(f"cover {i} does not start with the seed text")
         rest.append(_split_double_newlines(ids, tok))
+    return rest
+
+
+def _spans_by_rounds(rest: List[List[int]], seeds: Sequence[Any], contexts: Mapping[Any, List[int]], lm,
+                     quality: Optional[Mapping[str, object]], labels=None) -> List[List[List[int]]]:
+    """The round-based span search of :func:`texts_to_spans` over the covers' ids after their seeds (``rest``; the
+    lists are replaced as spans are found): text i is decoded after ``contexts[seeds[i]]`` with the one ``quality``.
+    ``labels``: the texts' numbers in the caller's call, for the error messages."""
+    from .codec.errors import DecodeDivergenceError
+    from .lm.mock import MockLM
+    from .stego import _quality_args, _takes_contexts
+
+    rest = list(rest)
+    q = _quality_args(quality)
+    finish = bool(q.get("finish_sent")) and hasattr(lm, "sentence_end_table")
+    sent_end = lm.sentence_end_table() if finish else None
     if hasattr(lm, "decode_counted_repair"):
         entry = lm.decode_counted_repair
     elif hasattr(lm, "decode_counted"):
@@ -399,8 +409,8 @@ def texts_to_spans(texts: Sequence[str], *, seed_text: Optional[str] = None,
             bits_l, counts_l = entry(lists, *args, quality=q, done=settled, **ckw)
         return bits_l, counts_l, lists, edits_l, orig
 
-    spans: List[List[List[int]]] = [[] for _ in texts]
-    active = [i for i in range(len(texts)) if rest[i]]
+    spans: List[List[List[int]]] = [[] for _ in rest]
+    active = [i for i in range(len(rest)) if rest[i]]
     while active:
         distinct = list(dict.fromkeys(seeds[i] for i in active))
         if len(distinct) == 1:
@@ -418,7 +428,8 @@ def texts_to_spans(texts: Sequence[str], *, seed_text: Optional[str] = None,
             b, c, l, ed, o = ends[i]
             end = _span_end(b, c, l, finish, sent_end)
             if end is None:
-                raise DecodeDivergenceError(f"cover {i}: no complete packet in the remaining {len(l)} tokens")
+                raise DecodeDivergenceError(f"cover {labels[i] if labels is not None else i}: no complete packet in "
+                                            f"the remaining {len(l)} tokens")
             # the list as it stood after the last repair inside the span (later "repairs" decoded the next span's
             # tokens out of context); a repair at the span's end may have split a cross-boundary merge, whose
             # suffix tokens start the next span
@@ -429,6 +440,57 @@ def texts_to_spans(texts: Sequence[str], *, seed_text: Optional[str] = None,
                 nxt.append(i)
         active = nxt
     return spans
+
+
+def texts_to_spans(texts: Sequence[str], *, seed_text: Optional[str] = None,
+                   seed_texts: Optional[Sequence[str]] = None, lm,
+                   quality: Optional[Mapping[str, object]] = None,
+                   qualities: Optional[Sequence[Optional[Mapping[str, object]]]] = None,
+                   slots: Optional[int] = None) -> List[List[List[int]]]:
+    """Recover the token spans of many cover texts (the inverse of ``spans_to_text``, which the reference leaves
+    unimplemented, ``codec/textio.py:58-63``).  The text is re-tokenised, the seed's ids are stripped, and the
+    spans are found one per round: every cover's next span is decoded as one stream of a lockstep batch, the
+    packet completes at a known token and the span ends there or, with ``finish_sent``, at the following
+    sentence end.  A text that re-tokenises differently from the emitted ids (GPT-2 BPE merges, also across
+    span boundaries) is repaired while decoding with the reference's heuristics (``code_base/arithmetic.py:
+    233-242,300-342``, the provider's ``decode_counted_repair``): the spans are the repaired ids.
+
+    Exactly one of ``seed_text`` (shared) and ``seed_texts`` (one per text) is given.  With ``seed_texts`` every
+    text is stripped of its own seed and decoded after its own context: one lockstep batch with one context per
+    stream on a provider whose counted decodes take ``contexts=``, one batch per distinct context otherwise.
+
+    ``qualities`` (one mapping per text, instead of ``quality``): every text is decoded with its own quality -- the
+    covers of one ``cover_generate_batch`` call were accepted at different attempts, each with that attempt's
+    overrides.  With ``qualities`` or ``slots`` a provider that has ``reveal_spans`` (the HIP provider) finds the
+    spans of all texts in one slot-scheduled batch through ``slots`` slots; any other provider is called as without
+    them, once per distinct quality, results in the caller's order.  Without both the call is the round-based one
+    described above."""
+    tok = _tokenizer_of(lm)
+    seed_text, seeds = _one_or_many_seeds(seed_text, seed_texts, len(texts))
+    if seeds is None:
+        seeds = [seed_text] * len(texts)
+    per_q = _text_qualities(quality, qualities, len(texts))
+    if slots is not None and int(slots) < 1:
+        raise ConfigurationError("slots must be positive")
+    contexts = {s: list(lm.encode_seed(s)) for s in set(seeds)}
+    rest = _cover_rests(texts, seeds, tok)
+    if per_q is None and slots is None:
+        return _spans_by_rounds(rest, seeds, contexts, lm, quality)
+    from .stego import _quality_args
+
+    merged = [_quality_args(q) for q in per_q] if per_q is not None else [_quality_args(quality)] * len(texts)
+    if hasattr(lm, "reveal_spans"):
+        return lm.reveal_spans(rest, contexts=[contexts[s] for s in seeds], qualities=merged, slots=slots)
+    groups: Dict[str, List[int]] = {}
+    for i, q in enumerate(merged):
+        groups.setdefault(_quality_key(q), []).append(i)
+    out: List[Any] = [None] * len(texts)
+    for members in groups.values():
+        got = _spans_by_rounds([rest[i] for i in members], [seeds[i] for i in members], contexts, lm,
+                               merged[members[0]], labels=members)
+        for i, sp in zip(members, got):
+            out[i] = sp
+    return out
 
 
 def _looks_like_spans_json(text: str) -> bool:
@@ -442,16 +504,40 @@ def _looks_like_spans_json(text: str) -> bool:
 def cover_reveal_batch(cover_texts: Sequence[str], *, seed_text: Optional[str] = None,
                        seed_texts: Optional[Sequence[str]] = None, quality: Optional[Mapping[str, object]] = None,
                        use_crc: bool = True, ecc: str = "rs", nsym: int = 10, lm=None,
-                       return_errors: bool = False) -> List[Any]:
+                       return_errors: bool = False,
+                       qualities: Optional[Sequence[Optional[Mapping[str, object]]]] = None,
+                       attempts: Optional[Sequence[Attempt]] = None, slots: Optional[int] = None) -> List[Any]:
     """:func:`cover_reveal` for many covers: spans of all texts recovered round by round in lockstep batches,
     then one batched ``stego_decode``.  Exactly one of ``seed_text`` (shared) and ``seed_texts`` (one per cover: the
-    seed of the attempt that produced it, ``cover_generate_batch(..., return_attempts=True)``) is given."""
+    seed of the attempt that produced it, ``cover_generate_batch(..., return_attempts=True)``) is given.
+
+    ``qualities`` (one mapping per cover, instead of ``quality``) reveals every cover with its own quality;
+    ``attempts`` -- the :class:`Attempt` objects ``cover_generate_batch(return_attempts=True)`` returned with the
+    covers -- is shorthand for ``seed_texts=[a.seed_text ...]`` and ``qualities=[{**quality, **a.overrides} ...]``, so
+    the output of one ``cover_generate_batch`` call is revealed in one call whatever attempt accepted each cover
+    (``attempts`` with ``seed_text``, ``seed_texts`` or ``qualities``: ``ConfigurationError``).  With ``qualities``,
+    ``attempts`` or ``slots`` the spans are found by :func:`texts_to_spans` with them (one slot-scheduled batch on the
+    HIP provider), and every packet of a cover is decoded with its cover's quality."""
     from .stego import stego_decode_batch
 
-    seed_text, seeds = _one_or_many_seeds(seed_text, seed_texts, len(cover_texts))
+    n = len(cover_texts)
+    if attempts is not None:
+        if seed_text is not None or seed_texts is not None or qualities is not None:
+            raise ConfigurationError("attempts already gives every cover's seed and quality: give neither "
+                                     "seed_text / seed_texts nor qualities with it")
+        attempts = list(attempts)
+        if len(attempts) != n:
+            raise ConfigurationError(f"{len(attempts)} attempts for {n} covers")
+        base = normalise_quality(quality)
+        seed_texts = [a.seed_text for a in attempts]
+        qualities = [{**base, **normalise_quality(a.overrides)} for a in attempts]
+        quality = None
+    seed_text, seeds = _one_or_many_seeds(seed_text, seed_texts, n)
     provider = _ensure_cover_lm(lm)
+    per_q = _text_qualities(quality, qualities, n)
     q = normalise_quality(quality)
-    span_sets: List[Any] = [None] * len(cover_texts)
+    qkw = {"quality": q} if per_q is None else {"qualities": per_q}
+    span_sets: List[Any] = [None] * n
     plain = []
     for i, text in enumerate(cover_texts):
         if _looks_like_spans_json(text):
@@ -460,18 +546,22 @@ def cover_reveal_batch(cover_texts: Sequence[str], *, seed_text: Optional[str] =
             plain.append(i)
     if plain:
         skw = {"seed_text": seed_text} if seeds is None else {"seed_texts": [seeds[i] for i in plain]}
-        for i, sp in zip(plain, texts_to_spans([cover_texts[i] for i in plain], lm=provider, quality=q, **skw)):
+        tkw = {"quality": q} if per_q is None else {"qualities": [per_q[i] for i in plain]}
+        if slots is not None:
+            tkw["slots"] = slots
+        for i, sp in zip(plain, texts_to_spans([cover_texts[i] for i in plain], lm=provider, **tkw, **skw)):
             span_sets[i] = sp
     skw = {"seed_text": seed_text} if seeds is None else {"seed_texts": seeds}
-    return stego_decode_batch(span_sets, use_crc=use_crc, ecc=ecc, nsym=nsym, quality=q, lm=provider,
-                              return_errors=return_errors, **skw)
+    return stego_decode_batch(span_sets, use_crc=use_crc, ecc=ecc, nsym=nsym, lm=provider,
+                              return_errors=return_errors, **qkw, **skw)
 
 
 def cover_reveal(cover_text: str, *, seed_text: str, quality: Optional[Mapping[str, object]] = None,
-                 use_crc: bool = True, ecc: str = "rs", nsym: int = 10, lm=None) -> bytes:
+                 use_crc: bool = True, ecc: str = "rs", nsym: int = 10, lm=None,
+                 slots: Optional[int] = None) -> bytes:
     """``api.py:665-704``: a JSON spans payload is decoded as in the reference; a cover TEXT has its spans
     recovered by :func:`texts_to_spans` (the reference's ``text_to_spans`` raises ``NotImplementedError``,
-    after which it can only parse JSON), then ``stego_decode``."""
+    after which it can only parse JSON), then ``stego_decode``.  ``slots`` is passed on to :func:`texts_to_spans`."""
     provider = _ensure_cover_lm(lm)
     q = normalise_quality(quality)
     if _looks_like_spans_json(cover_text):
@@ -481,8 +571,9 @@ def cover_reveal(cover_text: str, *, seed_text: str, quality: Optional[Mapping[s
         try:
             if tok is None:
                 raise NotImplementedError
+            skw = {} if slots is None else {"slots": slots}
             spans = text_to_spans(cover_text, seed_to_ids(seed_text, tok), tok, lm=provider, quality=q,
-                                  seed_text=seed_text)
+                                  seed_text=seed_text, **skw)
         except NotImplementedError:
             spans = _parse_spans_payload(cover_text)
     return stego_decode(spans, use_crc=use_crc, ecc=ecc, nsym=nsym, quality=q, seed_text=seed_text, lm=provider)

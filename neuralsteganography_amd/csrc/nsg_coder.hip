@@ -783,7 +783,7 @@ __global__ __launch_bounds__((NSPLIT > 1 ? NSPLIT : WPB) * WAVE, NSG_MIN_WAVES_P
             return;
         }
     } else {
-        if (p.active && !p.active[b]) return;
+        if (DECODE ? decode_skipped(p, b, st.ntokens) : (p.active && !p.active[b])) return;
         if (!DECODE && sample_parked(p, b, st.ntokens)) return;  // past its length: nothing is written
     }
 
@@ -1418,7 +1418,7 @@ __global__ __launch_bounds__((NSPLIT > 1 ? NSPLIT : WPB) * WAVE, NSG_MIN_WAVES_P
         }
         if (sel < 0) err = NS_ST_ERR_RANGE;
     } else {
-        const int32_t tok = p.in_token[b];
+        const int32_t tok = decode_token(p, b, st.ntokens);
         if (tok >= 0 && tok < V && !is_banned(p, tok)) {
             const uint64_t kt = make_key(Elem<T>::load1(rowc, tok), (uint32_t)tok);
 #pragma unroll
@@ -1496,7 +1496,7 @@ __global__ __launch_bounds__((NSPLIT > 1 ? NSPLIT : WPB) * WAVE, NSG_MIN_WAVES_P
         const int n = diff == 0ull ? P - 1 : P - (64 - __builtin_clzll(diff));
         ns_stream_state ns = st;
         if (DECODE) {
-            const bool last = p.is_last[b] != 0;
+            const bool last = decode_is_last(p, b, st.ntokens);
             const int cntb = last ? P : n;
             const uint64_t src = last ? new_lo : top;
             if (lane == 0) {
@@ -1522,6 +1522,8 @@ __global__ __launch_bounds__((NSPLIT > 1 ? NSPLIT : WPB) * WAVE, NSG_MIN_WAVES_P
             if (!DECODE) {
                 p.out_token[b] = token;
                 if (p.hist && st.ntokens < p.hist_stride) p.hist[(int64_t)b * p.hist_stride + st.ntokens] = token;
+            } else {
+                decode_record(p, b, st.ntokens, ns.bit_pos, token);
             }
             if (p.trace) {
                 ns_step_trace tr;
@@ -1707,7 +1709,7 @@ static bool launch(ns_ctx* ctx, const nsg::StepParams& p, hipStream_t s) {
 
 extern "C" {
 
-const char* ns_version(void) { return "nsgcoder 0.31.5 gfx950"; }
+const char* ns_version(void) { return "nsgcoder 0.31.6 gfx950"; }
 
 int ns_set_split_max_batch(int max_batch) {
     const int prev = split_setting();
@@ -1994,6 +1996,43 @@ int ns_sample_step_streams(ns_ctx* ctx, const void* d_logits, int64_t ld, int B,
     const bool ok = p.K > ns_max_topk(ctx->dtype) ? nsg_wide_launch(ctx, p, false, (hipStream_t)hip_stream)
                                                   : launch<false>(ctx, p, (hipStream_t)hip_stream);
     if (!ok) return fail(ctx, NS_ERR_HIP, "ns_sample_step_streams: launch failed");
+    return NS_OK;
+}
+
+int ns_decode_step_streams(ns_ctx* ctx, const void* d_logits, int64_t ld, int B, const ns_stream_quality* d_quality,
+                           int k_max, const int32_t* d_tokens, int64_t tok_stride, const int32_t* d_length,
+                           ns_stream_state* d_state, uint8_t* d_out_bits, int64_t out_stride, int64_t* d_counts,
+                           int64_t counts_stride, int32_t* d_out_token, const int32_t* banned, int nbanned,
+                           ns_step_trace* d_trace, uint32_t step_flags, void* hip_stream) {
+    if (!ctx) return fail(ctx, NS_ERR_CONFIG, "null context");
+    if (ctx->dtype == NS_DTYPE_F64)
+        return fail(ctx, NS_ERR_CONFIG, "ns_decode_step_streams: a NS_DTYPE_F64 context holds provider probability rows (rank coder only)");
+    if (ctx->quality) return fail(ctx, NS_ERR_CONFIG, "ns_decode_step_streams: a stream quality table is registered");
+    if (!d_quality || !d_tokens || !d_length || !d_counts || !d_out_token || !d_out_bits)
+        return fail(ctx, NS_ERR_CONFIG, "ns_decode_step_streams: null table or output pointer");
+    if ((((uintptr_t)d_quality | (uintptr_t)d_counts) & 7u) != 0u ||
+        (((uintptr_t)d_tokens | (uintptr_t)d_length | (uintptr_t)d_out_token) & 3u) != 0u)
+        return fail(ctx, NS_ERR_CONFIG, "ns_decode_step_streams: misaligned table (quality and counts 8 bytes, int32 rows 4)");
+    if (k_max < 1 || tok_stride < 1 || counts_stride < 1 || out_stride < 1)
+        return fail(ctx, NS_ERR_CONFIG, "ns_decode_step_streams: k_max and the strides must be positive");
+    nsg::StepParams p;
+    // every host decision follows k_max alone (the rows' temperature, topk and precision are read by the kernels)
+    int rc = prepare(ctx, p, d_logits, ld, B, 1.0, k_max, banned, nbanned, d_trace, step_flags, d_state);
+    if (rc != NS_OK) return rc;
+    p.quality = d_quality;
+    p.dec_tokens = d_tokens;
+    p.dec_tok_stride = tok_stride;
+    p.dec_length = d_length;
+    p.dec_counts = d_counts;
+    p.dec_counts_stride = counts_stride;
+    p.out_token = d_out_token;
+    p.ranked = ctx->ranked;
+    p.ranked_stride = ctx->ranked_stride;
+    p.out_bits = d_out_bits;
+    p.out_stride = out_stride;
+    const bool ok = p.K > ns_max_topk(ctx->dtype) ? nsg_wide_launch(ctx, p, true, (hipStream_t)hip_stream)
+                                                  : launch<true>(ctx, p, (hipStream_t)hip_stream);
+    if (!ok) return fail(ctx, NS_ERR_HIP, "ns_decode_step_streams: launch failed");
     return NS_OK;
 }
 

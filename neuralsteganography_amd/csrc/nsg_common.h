@@ -326,7 +326,41 @@ struct StepParams {
     // per-stream quality rows of the rank coder (ns_rank_*_step_streams), nullable: then inv_temp, c32 and the rk_
     // policy fields above hold for every stream
     const ns_rank_stream_quality* rk_rows;
+    // per-stream token rows of the decode step (ns_decode_step_streams), dec_tokens nullable: then in_token, is_last
+    // and active above give the step's token per row.  With them, stream b's token index is its own ntokens: token
+    // dec_tokens[b * dec_tok_stride + ntokens], last at ntokens == dec_length[b] - 1, parked at ntokens >=
+    // dec_length[b]; the new bit_pos goes to dec_counts[b * dec_counts_stride + ntokens], the token to out_token[b]
+    const int32_t* dec_tokens;
+    int64_t dec_tok_stride;
+    const int32_t* dec_length;
+    int64_t* dec_counts;
+    int64_t dec_counts_stride;
 };
+
+// Decode stream b (wave- or block-uniform) takes no step: masked by the call's active row, or -- with token rows -- past
+// its length.  A token index outside a row of either table (a length beyond a stride) parks the stream as well, so
+// no index leaves its row.
+__device__ __forceinline__ bool decode_skipped(const StepParams& p, int b, int ntokens) {
+    if (p.dec_tokens) {
+        const int len = __builtin_amdgcn_readfirstlane(p.dec_length[b]);
+        return ntokens < 0 || ntokens >= len || ntokens >= p.dec_tok_stride || ntokens >= p.dec_counts_stride;
+    }
+    return p.active && !p.active[b];
+}
+// The token stream b receives this step and whether it is the stream's last (not skipped: decode_skipped).
+__device__ __forceinline__ int32_t decode_token(const StepParams& p, int b, int ntokens) {
+    return p.dec_tokens ? p.dec_tokens[(int64_t)b * p.dec_tok_stride + ntokens] : p.in_token[b];
+}
+__device__ __forceinline__ bool decode_is_last(const StepParams& p, int b, int ntokens) {
+    return p.dec_tokens ? ntokens == p.dec_length[b] - 1 : p.is_last[b] != 0;
+}
+// After a successful step of token t = ntokens (the lane that wrote the state): the bit count and the consumed token.
+__device__ __forceinline__ void decode_record(const StepParams& p, int b, int ntokens, int64_t bit_pos, int32_t token) {
+    if (p.dec_tokens) {
+        p.dec_counts[(int64_t)b * p.dec_counts_stride + ntokens] = bit_pos;
+        p.out_token[b] = token;
+    }
+}
 
 // The quality of stream b (wave-uniform): its table row, or the call's scalars.  b is wave-uniform, so the row is
 // read once at entry and every field is pinned to scalar registers.  K is clamped to the call's k_max (p.K), the

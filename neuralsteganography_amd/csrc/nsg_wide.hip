@@ -434,7 +434,7 @@ __device__ __forceinline__ void wide_finish(const StepParams& p, int P, int b, c
     const int32_t token = (int32_t)wkey_id(sel_key);
     ns_stream_state ns = st;
     if (DECODE) {
-        const bool last = p.is_last[b] != 0;
+        const bool last = decode_is_last(p, b, st.ntokens);
         const int cntb = last ? P : n;
         const uint64_t src = last ? new_lo : top;
         uint8_t* ob = p.out_bits + (int64_t)b * p.out_stride;
@@ -457,6 +457,8 @@ __device__ __forceinline__ void wide_finish(const StepParams& p, int P, int b, c
     if (!DECODE) {
         p.out_token[b] = token;
         if (p.hist && st.ntokens < p.hist_stride) p.hist[(int64_t)b * p.hist_stride + st.ntokens] = token;
+    } else {
+        decode_record(p, b, st.ntokens, ns.bit_pos, token);
     }
     if (p.trace) {
         ns_step_trace tr = {k, kp, sel, n, token, exact ? 1 : 0, S_used};
@@ -684,7 +686,7 @@ __device__ __forceinline__ void wide_cdf_stream(const StepParams& p, const WideS
             return false;
         });
     } else {
-        const int32_t tok = p.in_token[b];
+        const int32_t tok = decode_token(p, b, st.ntokens);
         if (tok >= 0 && tok < p.V && !is_banned(p, tok)) {
             const uint64_t kt = wkey(Elem<T>::load1(rowc, tok), (uint32_t)tok);
             for (int i = i0; i < min(i1, kp); ++i)
@@ -1111,7 +1113,7 @@ __device__ __forceinline__ void fast_tail(const StepParams& p, const RowQuality&
             if (r < nr && i < kp && (uint64_t)(cum[r] + shift) > idx) sel = min(sel, i);
         }
     } else {
-        const int32_t tok = p.in_token[b];
+        const int32_t tok = decode_token(p, b, st.ntokens);
         if (tok >= 0 && tok < p.V && !is_banned(p, tok)) {
             const char* rowc = (const char*)p.logits + (int64_t)b * p.ld * (int64_t)sizeof(T);
             const uint64_t kt = wkey(Elem<T>::load1(rowc, tok), (uint32_t)tok);
@@ -1260,7 +1262,7 @@ __global__ __launch_bounds__(FAST_THREADS, NSG_FAST_WAVES_PER_SIMD) void wide_on
         if (tid == 0 && !(p.flags & NS_STEP_FINISH_SENT)) p.state[b].flags = st.flags | NS_ST_DONE;
         active = false;
     }
-    if (DECODE && p.active && !p.active[b]) active = false;
+    if (DECODE && decode_skipped(p, b, st.ntokens)) active = false;
     // a sampler stream past its length (ns_sample_step_streams) is parked like a finished encode stream: off the
     // work list, nothing of it written
     if (!DECODE && p.sample && sample_parked(p, b, st.ntokens)) active = false;

@@ -766,6 +766,86 @@ class HipArithmeticLM:
             logits = self._lm_step(torch.tensor(feed, device=self.device, dtype=torch.long), nxt)
         return sess.bits(), counts, lists, edits
 
+    def reveal_spans(self, id_lists: Sequence[Sequence[int]], *, context: Optional[Sequence[int]] = None,
+                     contexts: Optional[Sequence[Sequence[int]]] = None,
+                     quality: Optional[Mapping[str, object]] = None,
+                     qualities: Optional[Sequence[Mapping[str, object]]] = None, slots: Optional[int] = None,
+                     check_every: int = 16, graphs: Optional[bool] = None) -> List[List[List[int]]]:
+        """The spans of many cover texts, given each text's ids after its seed: text i is cut into the spans its
+        sender encoded after ``contexts[i]`` (else ``context``) with ``qualities[i]`` (else ``quality``; the merged
+        quality, ``finish_sent`` included -- it may differ per text).  On the native GPU model (no attention window)
+        the texts run as ONE slot-scheduled batch (:class:`~neuralsteganography_amd.lm.slots.SlotRevealer`,
+        ``ns_decode_step_streams``): a slot decodes a text's remainder until its span settles, the rest is queued as
+        a fresh stream, and top-k values beyond the single-pass limit form a second group on the wide kernels (at
+        most two groups a call).  A text whose ids leave the kept top-k before a span settles (a cover that
+        re-tokenised differently from the emitted ids) leaves the batch; such texts, and every text on another LM,
+        run through the round-based code of ``cover.texts_to_spans`` with :meth:`decode_counted_repair` -- the BPE
+        repair -- once per distinct quality, so a text's spans are what that path returns for it.
+        ``last_reveal_schedule``: ``spans``, ``fallback_texts``, ``steps``, ``discarded_tokens`` (decoded past a
+        span's end before the check that noticed it), ``evictions``, ``compactions``, ``prefill_rows``,
+        ``kv_pages_peak``, ``quality_groups``."""
+        from ..cover import _quality_key, _spans_by_rounds
+
+        n = len(id_lists)
+        context, contexts = _one_or_many(context, contexts, n)
+        if (quality is None) == (qualities is None):
+            raise ConfigurationError("give exactly one of quality (shared) and qualities (one per text)")
+        qs = [dict(q or {}) for q in qualities] if qualities is not None else [dict(quality)] * n
+        if len(qs) != n:
+            raise ConfigurationError(f"{len(qs)} qualities for {n} texts")
+        if slots is not None and int(slots) < 1:
+            raise ConfigurationError("slots must be positive")
+        rest = [[int(t) for t in ids] for ids in id_lists]
+        for tl in rest:  # received ids feed the embedding gather: validate on the host first
+            if any(not 0 <= t < self.vocab for t in tl):
+                raise ConfigurationError(f"received token id outside [0, {self.vocab})")
+        ctxs = contexts if contexts is not None else [list(context)] * n
+        spans: List[List[List[int]]] = [[] for _ in range(n)]
+        sched = dict.fromkeys(REVEAL_SCHEDULE_KEYS, 0)
+        todo = [i for i in range(n) if rest[i]]
+        if todo and getattr(self.lm, "native", False) and not getattr(self.lm, "window", 0):
+            from .slots import SlotRevealer
+
+            plist = [coder_params_from_quality(qs[i], self.vocab, self.logits_dtype, self.banned) for i in todo]
+            finishes = [bool(qs[i].get("finish_sent")) for i in todo]
+            sent_end = self.sentence_end_table() if any(finishes) else None
+            groups = _quality_groups(plist, self._single_pass_limit(), mix_wide=True)
+            left = []
+            for members in groups:
+                sq = StreamQuality([plist[j] for j in members])
+                S = max(1, min(len(members), int(slots) if slots else self.max_batch))
+                rev = SlotRevealer(self, self._coder(sq.context_params(), S, mixed=True),
+                                   [rest[todo[j]] for j in members], [ctxs[todo[j]] for j in members], sq,
+                                   [finishes[j] for j in members], sent_end, slots=S,
+                                   use_graph=graphs is None or bool(graphs), labels=[todo[j] for j in members],
+                                   check_every=check_every, compact=self.slot_compaction, share=self.share_contexts,
+                                   share_prefixes=self.share_prefixes)
+                rev.run()
+                for k, j in enumerate(members):
+                    spans[todo[j]] = rev.spans[k]
+                    rest[todo[j]] = rev.rest[k] if k in rev.fallback else []
+                left += [todo[members[k]] for k in rev.fallback]
+                sched["kv_pages_peak"] = max(sched["kv_pages_peak"], rev.kv_peak)
+                for key, v in (("steps", rev.steps), ("discarded_tokens", rev.discarded),
+                               ("evictions", rev.evictions), ("compactions", rev.compactions),
+                               ("prefill_rows", rev.prefill_rows)):
+                    sched[key] += v
+            sched["quality_groups"] = len(groups)
+            todo = sorted(left)
+        sched["fallback_texts"] = len(todo)
+        by_q: Dict[str, List[int]] = {}
+        for i in todo:  # the round-based path takes one quality per call
+            by_q.setdefault(_quality_key(qs[i]), []).append(i)
+        for members in by_q.values():
+            got = _spans_by_rounds([rest[i] for i in members], [tuple(ctxs[i]) for i in members],
+                                   {tuple(ctxs[i]): list(ctxs[i]) for i in members}, self, qs[members[0]],
+                                   labels=members)
+            for i, sp in zip(members, got):
+                spans[i] = spans[i] + sp
+        sched["spans"] = sum(len(s) for s in spans)
+        self.last_reveal_schedule = sched
+        return spans
+
     def sample_batch(self, B: int, length: int, context: Optional[Sequence[int]] = None, *,
                      contexts: Optional[Sequence[Sequence[int]]] = None, lengths: Optional[Sequence[int]] = None,
                      temperatures: Optional[Sequence[float]] = None, topks: Optional[Sequence[int]] = None,
@@ -889,6 +969,8 @@ class HipArithmeticLM:
 
 
 SAMPLE_SCHEDULE_KEYS = ("slots", "quality_groups", "prefill_rows", "compactions", "evictions", "kv_pages_peak")
+REVEAL_SCHEDULE_KEYS = ("spans", "fallback_texts", "steps", "discarded_tokens", "evictions", "compactions",
+                        "prefill_rows", "kv_pages_peak", "quality_groups")
 
 
 def sample_draw_keys(n: int, seeds, seed: int, stream_offset: int):

@@ -37,6 +37,11 @@ The rank coder (library 0.31.5) runs through the same loops: :class:`RankSlotEnc
 ``coder.RankStreamEncodeSession`` and :class:`RankSlotDecoder` is :class:`SlotSampler`'s loop over
 ``coder.RankStreamDecodeSession``, every slot with its message's row of the rank quality table
 (``ns_rank_stream_quality``: temperature and policy), given to ``ns_rank_*_step_streams`` with each step.
+
+The reveal from cover text (library 0.31.6) is :class:`SlotRevealer`, :class:`SlotSampler`'s loop over
+``coder.DecodeStreamsSession`` (``ns_decode_step_streams``) with one difference: a stream's end is not known in
+advance -- a span ends where its packet's JSON closes -- so every check asks ``cover._span_end`` about every live
+slot, and what is left of a text after a settled span is queued as a fresh stream.
 """
 
 from __future__ import annotations
@@ -1379,3 +1384,258 @@ class RankSlotDecoder(SlotSampler):
 
     def _load(self, sess, slots, msgs, nl) -> None:
         sess.load_slots(slots, [self.lists[m] for m in msgs], [self.hists[m] for m in msgs], self.qual.take(msgs))
+
+
+class SlotRevealer:
+    """Find the spans of many cover texts through ``slots`` slots (``coder.DecodeStreamsSession``,
+    ``ns_decode_step_streams``).  A unit of work is (text i, its remaining ids): one slot decodes it after text i's
+    context with text i's quality row.  Unlike the other decode loops the end of a unit is not known in advance -- a
+    span ends where the decoded packet's JSON closes (plus the ``finish_sent`` tail) -- so every host check gathers,
+    for every live slot, the state, the bits up to ``bit_pos`` and the bit count after each decoded token (written by
+    the coder kernel itself), and asks ``cover._span_end``:
+
+    * the span settles at ``end``: ``ids[:end + 1]`` is recorded, the slot's pages are released and
+      ``ids[end + 1:]`` is queued as a fresh stream of the same text -- the same context (prefilled again, or shared
+      through the registry with whoever holds it), a reset coder state.  The tokens decoded past ``end`` before the
+      check (the next span's, out of context) are discarded, as the round-based path discards them;
+    * the slot is flagged ``NS_ST_ERR_DIVERGE`` (or ``NS_ST_ERR_RANGE``) and nothing settled from the counts before
+      it: the text leaves the batch and its current remainder goes, unchanged, to ``fallback`` (the caller runs the
+      round-based code with the BPE repair on it).  A flag at or after a settled ``end`` is ignored;
+    * the remainder is fully decoded and nothing settled: ``DecodeDivergenceError`` ("no complete packet ...").
+
+    The loop -- admission, shared pages, the pipelined check, graph capture, eviction of the youngest on a full
+    device, compaction once the queue is drained -- is :class:`SlotSampler`'s.  The check reads a copy of the three
+    buffers taken in stream order at the PREVIOUS check (consistent among themselves), so a span is noticed one check
+    late and the GPU never waits for the host.  An evicted text is re-queued with its current remainder and decoded
+    again from that remainder's start: the same bits, a stream's result does not depend on its neighbours."""
+
+    def __init__(self, provider, ctx, id_lists, contexts, qualities, finishes, sent_end, *, slots: int,
+                 use_graph: bool, labels=None, check_every: int = 16, compact: bool = True, share: bool = True,
+                 share_prefixes: bool = True):
+        self.p, self.lm, self.ctx = provider, provider.lm, ctx
+        self.qual = qualities  # coder.StreamQuality, one row per text
+        self.N = len(id_lists)
+        self.S = max(1, min(int(slots), self.N))
+        self.rest = [[int(t) for t in ids] for ids in id_lists]
+        self.finish = [bool(f) for f in finishes]
+        self.sent_end = sent_end
+        self.labels = list(labels) if labels is not None else list(range(self.N))
+        self.contexts = _trimmed(contexts, self.N)
+        self.keys, self.shares = _multiplicity(self.contexts, share)
+        self.chains = _prefix_chains(self.contexts, share and share_prefixes and
+                                     getattr(self.lm, "prefix_sharing", False))
+        self.use_graph = use_graph
+        self.check_every, self.allow_compact = int(check_every), compact
+        self.spans: List[List[List[int]]] = [[] for _ in range(self.N)]
+        self.fallback: List[int] = []  # texts that left the batch on a divergence (their remainder is in ``rest``)
+        self.steps = self.discarded = self.prefill_rows = 0
+        self.compactions = self.evictions = self.kv_peak = 0
+
+    def run(self) -> List[List[List[int]]]:
+        import torch
+
+        from ..codec.errors import DecodeDivergenceError
+        from ..coder import DecodeStreamsSession
+        from ..cover import _span_end
+        from ..exceptions import PacketECCError
+        from ..stego import packet_prefix
+
+        lm, S = self.lm, self.S
+        Lmax = max(1, max(len(r) for r in self.rest))
+        order = np.argsort(-np.asarray([len(r) for r in self.rest]), kind="stable")  # longest first
+        budget = getattr(self.p, "slot_budget_tokens", None) or Lmax + 1
+        lm.begin_slots(S, 0, budget)
+        logits = torch.zeros((S, lm.ld), device=lm.device, dtype=lm.logits_dtype)
+        dev = logits.device
+        sess = DecodeStreamsSession(self.ctx, S, max_tokens=Lmax, k_max=self.qual.k_max,
+                                    max_precision=self.qual.max_precision, rank_export=False)
+        stop = torch.zeros(S, dtype=torch.int32, device=dev)
+        ctx_host = np.zeros(S, dtype=np.int64)
+        len_host = np.zeros(S, dtype=np.int64)
+        slot_msg = np.full(S, -1, dtype=np.int64)
+        slot_gen = np.zeros(S, dtype=np.int64)  # admissions per slot: a copy belongs to the unit it was taken of
+        queue = deque(i for i in order.tolist() if self.rest[i])
+        graph, gkey = None, None
+        admit_blocked = False
+        bad = _lib.NS_ST_ERR_DIVERGE | _lib.NS_ST_ERR_RANGE
+        pins = (_Pinned(), _Pinned(), _Pinned())
+
+        def body():
+            lm.step_static(sess.step(logits))
+
+        def park(sl):
+            sess.park_slots(sl)
+            stop[torch.as_tensor(np.asarray(sl, dtype=np.int64), device=dev)] = 0
+            len_host[sl] = 0
+
+        def copy_out():
+            """The three buffers as they stand in stream order now, on their way to pinned host memory."""
+            got = [pin.take(t) for pin, t in zip(pins, (sess.state, sess.out_bits, sess.counts))]
+            return got[-1][1], [g[0] for g in got], slot_gen.copy()
+
+        def packet_closed(data: bytes) -> bool:
+            """Whether the whole bytes decoded so far (LSB-first bits: the buffer's own bytes) begin with a complete
+            packet -- ``_span_end``'s own first test, on the same bytes."""
+            try:
+                packet_prefix(data)
+            except PacketECCError:
+                return False
+            return True
+
+        def settle(snap):
+            """Ask ``_span_end`` for every live slot whose unit the copy was taken of; returns the freed slots."""
+            ev, (st_h, ob_h, cn_h), gen_then = snap
+            ev.synchronize()
+            f = _state_fields(st_h)
+            ob, cn = ob_h.numpy(), cn_h.numpy()
+            freed = []
+            for s in np.nonzero((slot_msg >= 0) & (slot_gen == gen_then))[0].tolist():
+                i = int(slot_msg[s])
+                ids = self.rest[i]
+                nt = min(int(f["ntokens"][s]), len(ids))
+                flagged = bool(int(f["flags"][s]) & bad)
+                if nt == 0 and not flagged:
+                    continue
+                bp = int(f["bit_pos"][s])
+                end = None
+                if packet_closed(ob[s, : bp // 8].tobytes()):  # else _span_end has nothing to find: skip its bit loop
+                    bits = np.unpackbits(ob[s, : (bp + 7) // 8], bitorder="little")[:bp].tolist()
+                    end = _span_end(bits, cn[s, :nt].tolist(), ids, self.finish[i], self.sent_end)
+                if end is not None:
+                    self.spans[i].append(ids[: end + 1])
+                    self.rest[i] = ids[end + 1:]
+                    fed = int(lm.kv.lens_host[s] - ctx_host[s]) if not flagged else nt
+                    self.discarded += max(0, min(fed, len(ids)) - (end + 1))
+                    if self.rest[i]:
+                        queue.append(i)
+                elif flagged:
+                    self.fallback.append(i)
+                elif nt >= len(ids):
+                    raise DecodeDivergenceError(
+                        f"cover {self.labels[i]}: no complete packet in the remaining {len(ids)} tokens")
+                else:
+                    continue
+                freed.append(s)
+            return np.asarray(freed, dtype=np.int64)
+
+        t = 0
+        pipelined = self.use_graph
+        pending = None
+        try:
+            while True:
+                if t % self.check_every == 0:
+                    snap = pending if pipelined else (copy_out() if t else None)
+                    fin = settle(snap) if snap is not None else np.zeros(0, dtype=np.int64)
+                    if fin.size:
+                        lm.kv.release(fin)
+                        slot_msg[fin] = -1
+                        park(fin)
+                        admit_blocked = False
+                    live = slot_msg >= 0
+                    empty = np.nonzero(~live)[0]
+                    if queue and empty.size and not admit_blocked:
+                        room = lm.pool.free_pages + lm.pool.growable_pages() - int(live.sum()) - 1
+                        adm = _admissible(queue, self.contexts, self.check_every, empty.size, room, self.keys,
+                                          self.shares, lm.kv.entries, self.chains, lm.kv.prefixes)
+                        if adm:
+                            back = self._admit(sess, logits, stop, empty[:len(adm)], adm, slot_msg, slot_gen, len_host,
+                                               ctx_host)
+                            queue.extendleft(reversed(back))
+                            admit_blocked = bool(back)
+                            live = slot_msg >= 0
+                        if not live.any():
+                            m = queue[0]
+                            raise KVCapacityError(
+                                f"cover {self.labels[m]}: no device memory for the KV pages of its "
+                                f"{len(self.contexts[m])}-token context")
+                    # pages for the next check_every + 1 positions (never past a unit's last token); on a full device
+                    # the youngest units go back to the queue's front (decoded again from their remainder's start)
+                    while live.any():
+                        sl = np.nonzero(live)[0]
+                        upto = np.minimum(lm.kv.lens_host[sl] + self.check_every + 1, ctx_host[sl] + len_host[sl])
+                        if lm.kv.ensure(sl, upto).size == 0:
+                            break
+                        if sl.size == 1:
+                            raise KVCapacityError(f"cover {self.labels[int(slot_msg[sl[0]])]} "
+                                                  f"({int(len_host[sl[0]])} tokens left) needs more KV pages than the "
+                                                  "device holds")
+                        v = sl[np.argmin(lm.kv.lens_host[sl] - ctx_host[sl])]  # the youngest: fewest tokens decoded
+                        queue.appendleft(int(slot_msg[v]))
+                        lm.kv.release([v])
+                        park(np.asarray([v]))
+                        slot_msg[v] = -1
+                        live = slot_msg >= 0
+                        admit_blocked = True
+                        self.evictions += 1
+                    if not live.any():
+                        break
+                    if self.allow_compact and not queue and int(live.sum()) <= sess.B // 2 and sess.B > 1:
+                        keep = np.nonzero(live)[0]
+                        lm.kv.release(np.setdiff1d(np.arange(sess.B), keep))
+                        lm.kv.compact(keep)
+                        lm.B = lm.kv.B
+                        sess.compact(keep)
+                        ki = torch.as_tensor(keep, device=dev)
+                        stop = stop.index_select(0, ki).contiguous()
+                        logits = logits.index_select(0, ki).contiguous()
+                        slot_msg, len_host = slot_msg[keep].copy(), len_host[keep].copy()
+                        ctx_host, slot_gen = ctx_host[keep].copy(), slot_gen[keep].copy()
+                        self.compactions += 1
+                    lm.stop_len = stop  # a parked slot skips its attention (and appends no K/V)
+                    if pipelined:
+                        pending = copy_out()
+                key = _layout_key(sess.state, sess.tokmat, sess.nlen, sess.counts, sess.out_bits, sess.out_token,
+                                  sess.qtable, logits, stop, lm.kv.table, lm.kv.lens) + (lm.kv.version,)
+                if self.use_graph:
+                    if graph is None or key != gkey:
+                        graph = None
+                        lm.begin_static(logits)
+                        graph, gkey = _SlotGraph(body), key
+                    else:
+                        graph.replay()
+                else:
+                    lm.begin_static(logits)
+                    body()
+                lm.advance(1)
+                t += 1
+        finally:
+            if graph is not None:
+                torch.cuda.current_stream().synchronize()
+            lm.stop_len = None
+            del graph
+        self.steps = t
+        self.kv_peak = lm.kv.peak
+        return self.spans
+
+    def _admit(self, sess, logits, stop, slots, msgs, slot_msg, slot_gen, len_host, ctx_host):
+        """Admit the texts ``msgs`` (their current remainders) into ``slots``: pages for each context and the unit's
+        first positions, one ragged prefill of the contexts into those pages, each text's quality row and tokens with
+        a fresh coder state, each context's logits into its slot's row.  Returns the texts that could not be given
+        pages (back to the queue)."""
+        import torch
+
+        lm = self.lm
+        slots = np.asarray(slots, dtype=np.int64)
+        tl = np.asarray([len(self.contexts[m]) for m in msgs], dtype=np.int64)
+        nl = np.asarray([len(self.rest[m]) for m in msgs], dtype=np.int64)
+        chains = [self.chains[m] for m in msgs] if self.chains is not None else None
+        ok = _map_contexts(lm.kv, slots, [self.keys[m] for m in msgs], [self.shares[m] for m in msgs], tl,
+                           tl + np.minimum(self.check_every + 1, nl), chains)
+        back = [m for m, k in zip(msgs, ok) if not k]
+        slots, msgs, tl, nl = slots[ok], [m for m, k in zip(msgs, ok) if k], tl[ok], nl[ok]
+        if not msgs:
+            return back
+        first = lm.prefill_contexts([self.contexts[m] for m in msgs], slots, [self.shares[m] for m in msgs],
+                                    [self.chains[m] for m in msgs] if self.chains is not None else None)
+        self.prefill_rows += lm.last_prefill["rows"]
+        sess.load_slots(slots, [self.rest[m] for m in msgs], self.qual.take(msgs))
+        idx = torch.as_tensor(slots, device=logits.device)
+        # the attention is skipped once the cache length reaches context + tokens - 1: the logits after the unit's
+        # last token are never read
+        stop[idx] = torch.from_numpy((tl + nl - 1).astype(np.int32)).to(logits.device)
+        logits.index_copy_(0, idx, first.to(logits.dtype))
+        slot_msg[slots] = msgs
+        slot_gen[slots] += 1
+        ctx_host[slots] = tl
+        len_host[slots] = nl
+        return back
