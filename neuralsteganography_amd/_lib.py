@@ -42,7 +42,9 @@ EXPORTS = ("ns_create", "ns_destroy", "ns_last_error", "ns_version", "ns_max_top
            "ns_decode_attention_paged", "ns_lm_embed_ln_rows", "ns_lm_layernorm_rows", "ns_seq_attention_ragged",
            "ns_kv_copy_rows", "ns_seq_attention_ragged_past", "ns_decode_attention_paged_chunk",
            "ns_frac_create", "ns_frac_destroy", "ns_frac_last_error", "ns_frac_init", "ns_frac_encode_step",
-           "ns_frac_decode_step", "ns_frac_set_slots", "ns_frac_scratch_bytes")
+           "ns_frac_decode_step", "ns_frac_set_slots", "ns_frac_scratch_bytes",
+           "ns_huffman_encode_step", "ns_huffman_decode_step", "ns_huffman_decode_step_streams",
+           "ns_bins_encode_step", "ns_bins_decode_step", "ns_bins_decode_step_streams")
 NS_LM_EPI_STORE, NS_LM_EPI_GELU, NS_LM_EPI_RESIDUAL, NS_LM_EPI_STORE_F32 = 0, 1, 2, 3
 NS_KV_FP16, NS_KV_FP8 = 0, 1
 
@@ -266,6 +268,16 @@ def lib() -> ctypes.CDLL:
     L.ns_frac_set_slots.argtypes = [vp, vp, ci]
     L.ns_frac_scratch_bytes.restype = i64
     L.ns_frac_scratch_bytes.argtypes = [vp, ci, i64, i64, i64]
+    # fixed-block baseline coders (include/nsg_baseline.h); the bins entries take the word-to-bin table after block_size
+    u32 = ctypes.c_uint32
+    enc_tail = [vp, i64, vp, vp, vp, vp, i64, i32p, ci, vp, vp, u32, vp]
+    dec_tail = [vp, vp, vp, vp, i64, i32p, ci, vp, u32, vp]
+    dec_streams_tail = [vp, i64, vp, vp, vp, i64, vp, i64, vp, i32p, ci, vp, u32, vp]
+    for name, tail in (("encode_step", enc_tail), ("decode_step", dec_tail), ("decode_step_streams", dec_streams_tail)):
+        for coder, extra in (("huffman", []), ("bins", [vp])):
+            f = getattr(L, f"ns_{coder}_{name}")
+            f.restype = ci
+            f.argtypes = [vp, vp, i64, ci, ci] + extra + tail
     _lib = L
     return L
 

@@ -1601,3 +1601,283 @@ class RankStreamDecodeSession:
         if bad.size:
             raise DecodeDivergenceError(f"streams {bad.tolist()[:8]}: token not present in distribution")
         return pls
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Fixed-block baseline coders (include/nsg_baseline.h): code_base/huffman_baseline.py and code_base/block_baseline.py
+# ---------------------------------------------------------------------------------------------------------------
+BASELINE_MODES = ("huffman", "bins")
+
+
+def bins_permutation(vocab_size: int, block_size: int) -> np.ndarray:
+    """The vocabulary order ``block_baseline.get_bins`` shuffles (``np.random.seed(block_size)`` then
+    ``np.random.shuffle``): the same MT19937 stream from a private ``RandomState``, so numpy's global generator
+    is left alone."""
+    order = np.arange(int(vocab_size))
+    np.random.RandomState(int(block_size)).shuffle(order)
+    return order
+
+
+def bins_table(vocab_size: int, block_size: int) -> np.ndarray:
+    """uint8[vocab]: the bin of every id (``words2bin`` of ``block_baseline.get_bins``, block_baseline.py:9-24)."""
+    order = bins_permutation(vocab_size, block_size)
+    num_bins = 2 ** int(block_size)
+    words_per_bin = vocab_size / num_bins
+    table = np.zeros(int(vocab_size), dtype=np.uint8)
+    for j in range(num_bins):
+        table[order[int(j * words_per_bin):int((j + 1) * words_per_bin)]] = j
+    return table
+
+
+class BaselineSpec:
+    """One call's baseline coder: ``mode`` ("huffman" or "bins") and ``block_size`` (1..8, with 2**block_size ids
+    left after the ban), checked against a context; holds the device word-to-bin table of the bins coder."""
+
+    def __init__(self, ctx: CoderContext, mode: str, block_size: int, table=None):
+        if mode not in BASELINE_MODES:
+            raise ConfigurationError(f"mode must be one of {BASELINE_MODES}")
+        self.mode = mode
+        self.block = int(block_size)
+        self.K = baseline_leaders(ctx.params.vocab, ctx.params.banned_ids(), block_size)
+        if ctx.params.dtype not in ("f32", "f16"):
+            raise ConfigurationError("the baseline coders take fp32 or fp16 logits rows")
+        self.max_bits = self.K - 1 if mode == "huffman" else self.block  # bits one token can carry
+        self.table = None
+        if mode == "bins":
+            torch = _torch()
+            t = bins_table(ctx.params.vocab, self.block) if table is None else np.asarray(table, dtype=np.uint8)
+            if t.shape != (ctx.params.vocab,) or int(t.max(initial=0)) >= self.K:
+                raise ConfigurationError("the word-to-bin table needs one bin below 2**block_size per id")
+            self.table = torch.from_numpy(np.ascontiguousarray(t)).to(torch.device("cuda", ctx.device))
+
+    def entry(self, name: str):
+        return getattr(_lib.lib(), f"ns_{self.mode}_{name}")
+
+    def head(self, ctx: CoderContext, logits, B: int):
+        """The leading arguments every baseline entry point shares."""
+        args = [ctx._h, _ptr(logits), logits.stride(0), B, self.block]
+        if self.mode == "bins":
+            args.append(_ptr(self.table))
+        return args
+
+
+def baseline_leaders(vocab: int, banned: Sequence[int], block_size) -> int:
+    """K = 2**block_size after the checks every baseline entry point makes."""
+    if isinstance(block_size, bool) or not isinstance(block_size, (int, np.integer)) or not 1 <= int(block_size) <= 8:
+        raise ConfigurationError("block_size must be an integer within [1, 8]")
+    valid = int(vocab) - len({int(b) for b in banned if 0 <= int(b) < int(vocab)})
+    if (1 << int(block_size)) > valid:
+        raise ConfigurationError(f"2**block_size = {1 << int(block_size)} exceeds the {valid} ids left after the ban")
+    return 1 << int(block_size)
+
+
+class BaselineEncodeSession(EncodeSession):
+    """:class:`EncodeSession` of a baseline coder: the same payload, state, history and slot methods, one
+    ``ns_huffman_encode_step`` / ``ns_bins_encode_step`` per :meth:`step`.  ``stats=True`` accumulates the
+    reference's avg_NLL, avg_KL and words_per_bit (``avg_Hq`` has no counterpart and stays 0)."""
+
+    def __init__(self, ctx: CoderContext, payload_bits: Sequence[Sequence[int]], *, mode: str, block_size: int,
+                 max_tokens: Optional[int] = None, stats: bool = False, payload_stride: Optional[int] = None,
+                 table=None):
+        self.spec = BaselineSpec(ctx, mode, block_size, table)
+        super().__init__(ctx, payload_bits, max_tokens=max_tokens, stats=stats, payload_stride=payload_stride)
+
+    def step(self, logits, *, finish_sent: bool = False):
+        self._check_logits(logits)
+        flags = _lib.NS_STEP_FINISH_SENT if finish_sent else 0
+        rc = self.spec.entry("encode_step")(
+            *self.spec.head(self.ctx, logits, self.B), _ptr(self.payload), self.payload.stride(0), _ptr(self.nbits),
+            _ptr(self.state), _ptr(self.out_token), _ptr(self.hist), self.hist.shape[1], self.ctx._banned,
+            self.ctx._nbanned, _ptr(self.stats_acc), _ptr(self.trace), flags, _stream_handle())
+        self.ctx.check(rc, f"ns_{self.spec.mode}_encode_step")
+        self.steps += 1
+        return self.out_token
+
+    def raise_errors(self) -> None:
+        f = self.fields()["flags"]
+        bad = np.nonzero(f & _lib.NS_ST_ERR_RANGE)[0]
+        if bad.size:
+            raise ArithmeticRangeError(f"streams {bad.tolist()[:8]}: a row the {self.spec.mode} coder cannot code")
+
+
+class BaselineDecodeSession(DecodeSession):
+    """:class:`DecodeSession` of a baseline coder (lockstep: token t of every stream per step)."""
+
+    def __init__(self, ctx: CoderContext, token_lists: Sequence[Sequence[int]], *, mode: str, block_size: int,
+                 table=None):
+        self.spec = BaselineSpec(ctx, mode, block_size, table)
+        super().__init__(ctx, token_lists)
+        torch = _torch()
+        self.out_stride = int((self.T * self.spec.max_bits + 7) // 8 + 8)
+        self.out_bits = torch.zeros((self.B, self.out_stride), dtype=torch.uint8, device=self.state.device)
+        self.ranked = None
+        self.rank_stride = 0
+
+    def enable_export(self):
+        """Register a [B, K + 1] rank export for the steps of this session; returns it."""
+        torch = _torch()
+        self.rank_stride = self.spec.K + 1
+        self.ranked = torch.full((self.B, self.rank_stride), -1, dtype=torch.int32, device=self.state.device)
+        return self.ranked
+
+    def step(self, logits) -> None:
+        if self.t >= self.T:
+            raise ConfigurationError("all tokens already decoded")
+        t = self.t
+        _check_logits(self.ctx, self.B, logits)
+        L = _lib.lib()
+        if self.ranked is not None:
+            self.ctx.check(L.ns_set_rank_export(self.ctx._h, _ptr(self.ranked), self.rank_stride), "ns_set_rank_export")
+        rc = self.spec.entry("decode_step")(
+            *self.spec.head(self.ctx, logits, self.B), _ptr(self.tok[t]), _ptr(self.act[t]), _ptr(self.state),
+            _ptr(self.out_bits), self.out_stride, self.ctx._banned, self.ctx._nbanned, _ptr(self.trace), 0,
+            _stream_handle())
+        if self.ranked is not None:
+            L.ns_set_rank_export(self.ctx._h, ctypes.c_void_p(0), 0)
+        self.ctx.check(rc, f"ns_{self.spec.mode}_decode_step")
+        self.t += 1
+
+    def step_static(self, logits, **kw):
+        raise ConfigurationError("the baseline coders' table-driven decode is BaselineDecodeStreamsSession")
+
+    def bits(self) -> List[List[int]]:
+        f = _state_fields(self.state)
+        bad = np.nonzero(f["flags"] & _lib.NS_ST_ERR_RANGE)[0]
+        if bad.size:
+            raise ArithmeticRangeError(f"streams {bad.tolist()[:8]}: a row the {self.spec.mode} coder cannot code")
+        bad = np.nonzero(f["flags"] & _lib.NS_ST_ERR_DIVERGE)[0]
+        if bad.size:
+            raise DecodeDivergenceError(f"streams {bad.tolist()[:8]}: received token outside the {self.spec.mode} code")
+        return _bit_rows_to_lists(self.out_bits, f["bit_pos"])
+
+
+class BaselineStreamingDecodeSession(StreamingDecodeSession):
+    """:class:`StreamingDecodeSession` of a baseline coder: the host supplies each step's tokens (the text decoders'
+    BPE repairs edit the token lists mid-stream); a diverged stream exports its K ranked leaders (Huffman) or every
+    bin's token in bin order (bins)."""
+
+    def __init__(self, ctx: CoderContext, B: int, max_tokens: int, *, mode: str, block_size: int, table=None):
+        self.spec = BaselineSpec(ctx, mode, block_size, table)
+        super().__init__(ctx, B, max_tokens)
+        torch = _torch()
+        self.P = self.spec.max_bits
+        self.out_stride = int((max(1, max_tokens) * self.P + 7) // 8 + 8)
+        self.out_bits = torch.zeros((self.B, self.out_stride), dtype=torch.uint8, device=self.dev)
+        self.rank_stride = self.spec.K + 1
+        self.ranked = torch.full((self.B, self.rank_stride), -1, dtype=torch.int32, device=self.dev)
+
+    def step(self, logits, tokens: Sequence[int], active: Sequence[bool]) -> None:  # type: ignore[override]
+        torch = _torch()
+        _check_logits(self.ctx, self.B, logits)
+        f = _state_fields(self.state)
+        self._grow(int(f["bit_pos"].max(initial=0)) + 2 * self.P)
+        tok = torch.tensor(np.asarray(tokens, dtype=np.int32), device=self.dev)
+        act = torch.tensor(np.asarray(active, dtype=np.uint8), device=self.dev)
+        L = _lib.lib()
+        self.ctx.check(L.ns_set_rank_export(self.ctx._h, _ptr(self.ranked), self.rank_stride), "ns_set_rank_export")
+        rc = self.spec.entry("decode_step")(
+            *self.spec.head(self.ctx, logits, self.B), _ptr(tok), _ptr(act), _ptr(self.state), _ptr(self.out_bits),
+            self.out_stride, self.ctx._banned, self.ctx._nbanned, ctypes.c_void_p(0), 0, _stream_handle())
+        L.ns_set_rank_export(self.ctx._h, ctypes.c_void_p(0), 0)
+        self.ctx.check(rc, f"ns_{self.spec.mode}_decode_step")
+
+    def range_errors(self) -> List[int]:
+        f = _state_fields(self.state)["flags"]
+        return np.nonzero(f & _lib.NS_ST_ERR_RANGE)[0].tolist()
+
+
+class BaselineDecodeStreamsSession(DecodeStreamsSession):
+    """:class:`DecodeStreamsSession` of a baseline coder (``ns_huffman_decode_step_streams`` /
+    ``ns_bins_decode_step_streams``): every slot decodes the token at its own ``ntokens`` from its device token
+    row, so the slot loop needs no host read and one captured step serves every step."""
+
+    def __init__(self, ctx: CoderContext, S: int, *, max_tokens: int, mode: str, block_size: int, table=None,
+                 rank_export: bool = True):
+        torch = _torch()
+        self.spec = BaselineSpec(ctx, mode, block_size, table)
+        self.ctx, self.B = ctx, int(S)
+        if self.B < 1 or self.B > ctx.max_batch:
+            raise ConfigurationError(f"batch {self.B} outside [1, {ctx.max_batch}]")
+        dev = torch.device("cuda", ctx.device)
+        self.T = max(1, int(max_tokens))
+        self.k_max, self.P = self.spec.K, self.spec.max_bits
+        self.tokmat = torch.zeros((self.B, self.T), dtype=torch.int32, device=dev)
+        self.nlen = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        self.counts = torch.zeros((self.B, self.T), dtype=torch.int64, device=dev)
+        self.out_token = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        self.out_stride = int((self.T * self.P + 7) // 8 + 8)
+        self.out_bits = torch.zeros((self.B, self.out_stride), dtype=torch.uint8, device=dev)
+        self.qtable = None
+        self.state = _state_tensor(self.B, dev)
+        self.rank_stride = self.spec.K + 1
+        self.ranked = torch.full((self.B, self.rank_stride), -1, dtype=torch.int32, device=dev) if rank_export \
+            else None
+        self.trace = None
+        self.steps = 0
+
+    def step(self, logits):  # type: ignore[override]
+        _check_logits(self.ctx, self.B, logits)
+        L = _lib.lib()
+        if self.ranked is not None:
+            self.ctx.check(L.ns_set_rank_export(self.ctx._h, _ptr(self.ranked), self.rank_stride), "ns_set_rank_export")
+        rc = self.spec.entry("decode_step_streams")(
+            *self.spec.head(self.ctx, logits, self.B), _ptr(self.tokmat), self.T, _ptr(self.nlen), _ptr(self.state),
+            _ptr(self.out_bits), self.out_stride, _ptr(self.counts), self.T, _ptr(self.out_token), self.ctx._banned,
+            self.ctx._nbanned, _ptr(self.trace), 0, _stream_handle())
+        if self.ranked is not None:
+            L.ns_set_rank_export(self.ctx._h, ctypes.c_void_p(0), 0)
+        self.ctx.check(rc, f"ns_{self.spec.mode}_decode_step_streams")
+        self.steps += 1
+        return self.out_token
+
+    def load_slots(self, slots: Sequence[int], token_lists: Sequence[Sequence[int]], quality=None) -> None:
+        """Start new streams in ``slots``: their tokens and count, a zeroed state, output bytes and counts."""
+        torch = _torch()
+        n = len(slots)
+        if n == 0:
+            return
+        if len(token_lists) != n:
+            raise ConfigurationError("load_slots: one token list per slot")
+        tok = np.zeros((n, self.T), dtype=np.int32)
+        nl = np.zeros(n, dtype=np.int32)
+        for i, tl in enumerate(token_lists):
+            k = len(tl)
+            if k > self.T:
+                raise ConfigurationError("stream longer than the session was sized for")
+            tok[i, :k] = np.asarray(tl, dtype=np.int32)
+            nl[i] = k
+        dev = self.state.device
+        idx = torch.as_tensor(np.asarray(slots, dtype=np.int64), device=dev)
+        self.tokmat[idx] = torch.from_numpy(tok).to(dev)
+        self.nlen[idx] = torch.from_numpy(nl).to(dev)
+        self.state[idx] = 0
+        self.out_bits[idx] = 0
+        self.counts[idx] = 0
+
+
+def baseline_encode_batch(ctx: CoderContext, payload_bits: Sequence[Sequence[int]], logits_fn, *, mode: str,
+                          block_size: int, max_steps: int = 1 << 20, check_every: int = 32, finish_sent: bool = False,
+                          return_stats: bool = False, table=None):
+    """:func:`encode_batch` for a baseline coder: steps until every stream has consumed its payload (and, with
+    ``finish_sent``, ended its sentence); ``logits_fn(step, last_tokens)`` gives each step's ``[B, ld]`` logits."""
+    sess = BaselineEncodeSession(ctx, payload_bits, mode=mode, block_size=block_size, stats=return_stats, table=table)
+    last = sess.out_token
+    for t in range(max_steps):
+        if t % check_every == 0:
+            if sess.all_done():
+                break
+            sess.ensure_history(check_every)
+        last = sess.step(logits_fn(t, last), finish_sent=finish_sent)
+    else:
+        raise ConfigurationError("encode did not finish within max_steps")
+    if return_stats:
+        return sess.tokens(), sess.stats()
+    return sess.tokens()
+
+
+def baseline_decode_batch(ctx: CoderContext, token_lists: Sequence[Sequence[int]], logits_fn, *, mode: str,
+                          block_size: int, table=None) -> List[List[int]]:
+    sess = BaselineDecodeSession(ctx, token_lists, mode=mode, block_size=block_size, table=table)
+    for t in range(sess.T):
+        sess.step(logits_fn(t, sess.tok[t]))
+    return sess.bits()

@@ -766,6 +766,217 @@ class HipArithmeticLM:
             logits = self._lm_step(torch.tensor(feed, device=self.device, dtype=torch.long), nxt)
         return sess.bits(), counts, lists, edits
 
+    # ---------------------------------------------------------------- fixed-block baseline coders (Huffman, bins)
+    def _baseline_ctx(self, S: int, block_size: int) -> CoderContext:
+        """The coder context of a baseline call (vocab, dtype and banned ids; the arithmetic quality is unused),
+        after the block-size checks."""
+        from ..coder import baseline_leaders
+
+        params = CoderParams(vocab=self.vocab, precision=26, temp=1.0, topk=2, dtype=self.logits_dtype,
+                             banned=self.banned)
+        baseline_leaders(self.vocab, params.banned_ids(), block_size)
+        return self._coder(params, S)
+
+    def _baseline_groups(self, entry, items, contexts, nres: int, **kw):
+        """Non-native LMs: ``entry`` once per distinct context, ``nres`` per-message result lists in caller order."""
+        groups: Dict[tuple, List[int]] = {}
+        for i, c in enumerate(contexts):
+            groups.setdefault(tuple(c), []).append(i)
+        out = [[None] * len(items) for _ in range(nres)]
+        for c, members in groups.items():
+            res = entry([items[i] for i in members], list(c), **kw)
+            res = res if nres > 1 else (res,)
+            for k in range(nres):
+                for j, i in enumerate(members):
+                    out[k][i] = res[k][j]
+        return tuple(out) if nres > 1 else out[0]
+
+    def encode_baseline_batch(self, bit_lists: Sequence[Sequence[int]], context: Optional[Sequence[int]] = None, *,
+                              contexts: Optional[Sequence[Sequence[int]]] = None, mode: str, block_size: int,
+                              finish_sent: bool = False, return_stats: bool = False, slots: Optional[int] = None,
+                              graphs: Optional[bool] = None, check_every: int = 16):
+        """Encode bit lists with a fixed-block baseline coder: ``mode="huffman"`` (``code_base/huffman_baseline.py``)
+        or ``mode="bins"`` (``code_base/block_baseline.py``), ``block_size`` bits per block (1..8).  ``context`` /
+        ``contexts``, ``slots`` and ``graphs`` as in :meth:`encode_batch`: on the native model the messages run
+        through the slot scheduler (:class:`~neuralsteganography_amd.lm.slots.BaselineSlotEncoder`), and a message's
+        tokens and statistics equal those of its one-message call.  ``return_stats`` adds per message
+        ``avg_NLL``, ``avg_KL`` and ``words_per_bit`` as the reference returns them."""
+        from ..coder import BASELINE_MODES, BaselineEncodeSession
+
+        if mode not in BASELINE_MODES:
+            raise ConfigurationError(f"mode must be one of {BASELINE_MODES}")
+        B = len(bit_lists)
+        context, contexts = _one_or_many(context, contexts, B)
+        ctx = self._baseline_ctx(max(1, min(B, int(slots) if slots else self.max_batch)), block_size)
+        if B == 0:
+            return ([], []) if return_stats else []
+        kw = dict(mode=mode, block_size=block_size, finish_sent=finish_sent, return_stats=return_stats, slots=slots,
+                  graphs=graphs, check_every=check_every)
+        native = getattr(self.lm, "native", False)
+        if contexts is not None and not native:
+            return self._baseline_groups(self.encode_baseline_batch, bit_lists, contexts, 2 if return_stats else 1,
+                                         **kw)
+        if finish_sent:
+            ctx.set_sentence_end(self.sentence_end_table())
+        if native:
+            from .slots import BaselineSlotEncoder
+
+            S = max(1, min(B, int(slots) if slots else self.max_batch))
+            enc = BaselineSlotEncoder(self, ctx, bit_lists, context, mode=mode, block_size=block_size, slots=S,
+                                      finish=bool(finish_sent), stats=return_stats,
+                                      use_graph=True if graphs is None else bool(graphs), check_every=check_every,
+                                      compact=self.slot_compaction, contexts=contexts, share=self.share_contexts,
+                                      share_prefixes=self.share_prefixes)
+            toks, st = enc.run()
+            self.last_schedule = {"slots": S, "evictions": enc.evictions, "compactions": enc.compactions,
+                                  "max_live": enc.max_live, "kv_pages_peak": enc.kv_peak,
+                                  "prefill_rows": enc.prefill_rows, "prefill_groups": enc.prefill_groups,
+                                  "prefill_shared": enc.prefill_shared}
+            return (toks, st) if return_stats else toks
+        max_bits = max(len(b) for b in bit_lists)
+        budget = 2 * max_bits + 64
+        logits = self.lm.prefill(context, B, budget)
+        sess = BaselineEncodeSession(ctx, bit_lists, mode=mode, block_size=block_size, max_tokens=budget,
+                                     stats=return_stats)
+        toks = self._encode_loop(sess, lambda lg: sess.step(lg, finish_sent=finish_sent), logits, None, bit_lists,
+                                 check_every, 4096, max_bits + 4096 + 64)
+        return (toks, sess.stats()) if return_stats else toks
+
+    def decode_baseline_batch(self, token_lists: Sequence[Sequence[int]], context: Optional[Sequence[int]] = None, *,
+                              contexts: Optional[Sequence[Sequence[int]]] = None, mode: str, block_size: int,
+                              slots: Optional[int] = None, graphs: Optional[bool] = None,
+                              check_every: int = 16) -> List[List[int]]:
+        """Decode token lists (ragged) with a baseline coder; returns every emitted bit (callers truncate to the
+        payload length).  A token the coder cannot have emitted raises :class:`DecodeDivergenceError`
+        (:meth:`decode_baseline_repair` runs the reference's BPE repairs instead).  On the native model the lists
+        run through the slot scheduler with every slot's token read on the device
+        (:class:`~neuralsteganography_amd.lm.slots.BaselineSlotDecoder`)."""
+        from ..codec.errors import DecodeDivergenceError
+        from ..coder import BASELINE_MODES, BaselineDecodeSession
+
+        if mode not in BASELINE_MODES:
+            raise ConfigurationError(f"mode must be one of {BASELINE_MODES}")
+        B = len(token_lists)
+        context, contexts = _one_or_many(context, contexts, B)
+        S = max(1, min(B, int(slots) if slots else self.max_batch))
+        native = getattr(self.lm, "native", False)
+        ctx = self._baseline_ctx(S if native else max(B, 1), block_size)
+        if B == 0:
+            return []
+        kw = dict(mode=mode, block_size=block_size, slots=slots, graphs=graphs, check_every=check_every)
+        if contexts is not None and not native:
+            return self._baseline_groups(self.decode_baseline_batch, token_lists, contexts, 1, **kw)
+        for tl in token_lists:  # received ids feed the embedding gather: validate on the host first
+            if any((int(t) < 0 or int(t) >= self.vocab) for t in tl):
+                raise DecodeDivergenceError(f"received token id outside [0, {self.vocab})")
+        if native:
+            from .slots import BaselineSlotDecoder
+
+            out: List[List[int]] = [[] for _ in range(B)]
+            some = [i for i, tl in enumerate(token_lists) if len(tl)]
+            if not some:
+                return out
+            ctxs = contexts if contexts is not None else [context] * B
+            dec = BaselineSlotDecoder(self, ctx, [token_lists[i] for i in some], [ctxs[i] for i in some], mode=mode,
+                                      block_size=block_size, slots=min(S, len(some)),
+                                      use_graph=True if graphs is None else bool(graphs), check_every=check_every,
+                                      compact=self.slot_compaction, share=self.share_contexts,
+                                      share_prefixes=self.share_prefixes)
+            got, _ = dec.run()
+            for i, bits in zip(some, got):
+                out[i] = bits
+            self.last_decode_schedule = {"slots": dec.S, "evictions": dec.evictions, "compactions": dec.compactions,
+                                         "prefill_rows": dec.prefill_rows, "prefill_groups": dec.prefill_groups,
+                                         "prefill_shared": dec.prefill_shared}
+            return out
+        sess = BaselineDecodeSession(ctx, token_lists, mode=mode, block_size=block_size)
+        logits = self.lm.prefill(context, B, max(sess.T, 1) + 1)
+        for t in range(sess.T):
+            sess.step(logits)
+            if t + 1 < sess.T:
+                logits = self.lm.step(sess.tok[t])
+        return sess.bits()
+
+    def decode_baseline_repair(self, token_lists: Sequence[Sequence[int]], context: Optional[Sequence[int]] = None, *,
+                               contexts: Optional[Sequence[Sequence[int]]] = None, mode: str, block_size: int,
+                               enc=None):
+        """The token loops of ``decode_huffman`` / ``decode_block`` with the reference's BPE repairs
+        (huffman_baseline.py:108-149, block_baseline.py:140-181), round-based like :meth:`decode_counted_repair`: a
+        token the coder cannot have emitted diverges on the device with its state untouched, the host repairs the
+        token list from the exported ids (:func:`huffman_repair` over the K ranked leaders, :func:`bins_repair` over
+        every bin's token) and the step is re-issued.  An unrepairable token decodes as rank 0 (Huffman) or as the
+        last bin (bins) while the LM is fed the received token, as the reference does.  Returns ``(bits per stream,
+        repaired token lists)``."""
+        import torch
+
+        from ..coder import BASELINE_MODES, BaselineStreamingDecodeSession
+
+        if mode not in BASELINE_MODES:
+            raise ConfigurationError(f"mode must be one of {BASELINE_MODES}")
+        enc = enc if enc is not None else self.tokenizer
+        lists = [[int(t) for t in tl] for tl in token_lists]
+        B = len(lists)
+        context, contexts = _one_or_many(context, contexts, B)
+        ctx = self._baseline_ctx(max(B, 1), block_size)
+        if B == 0:
+            return [], []
+        if contexts is not None and not getattr(self.lm, "native", False):
+            return self._baseline_groups(self.decode_baseline_repair, lists, contexts, 2, mode=mode,
+                                         block_size=block_size, enc=enc)
+        for tl in lists:
+            if any(not 0 <= t < self.vocab for t in tl):
+                raise ConfigurationError(f"received token id outside [0, {self.vocab})")
+        cap = max((len(x) for x in lists), default=0) + 8
+        sess = BaselineStreamingDecodeSession(ctx, B, cap, mode=mode, block_size=block_size)
+        logits = self._prefill_streams(context, contexts, B, cap)
+        pos = [0] * B
+        last_bin = (1 << int(block_size)) - 1
+        while True:
+            active = [pos[b] < len(lists[b]) for b in range(B)]
+            if not any(active):
+                break
+            tok = [lists[b][pos[b]] if active[b] else 0 for b in range(B)]
+            sess.step(logits, tok, active)
+            feed = list(tok)
+            bad = sess.diverged()
+            if bad:
+                redo = [0] * B
+                for b in bad:
+                    ids = sess.ranked_ids(b)
+                    snapshot = list(lists[b])
+                    try:
+                        if mode == "huffman":
+                            redo[b] = huffman_repair(enc, lists[b], pos[b], ids)[0]
+                        else:
+                            bin_num, repaired = bins_repair(enc, lists[b], pos[b], ids)
+                            redo[b] = ids[bin_num] if repaired else ids[last_bin]
+                    except IndexError:  # the reference's merge reads past the end of the text and raises
+                        from ..codec.errors import DecodeDivergenceError
+
+                        lists[b][:] = snapshot
+                        raise DecodeDivergenceError(f"stream {b}: BPE repair at token {pos[b]} runs past the end of "
+                                                    "the text") from None
+                    if any(not 0 <= t < self.vocab for t in lists[b]):
+                        raise ConfigurationError(f"repair produced a token id outside [0, {self.vocab})")
+                    feed[b] = lists[b][pos[b]]  # the repaired token, or the received one when unrepairable
+                sess.clear(bad)
+                sess.step(logits, redo, [b in bad for b in range(B)])
+                if sess.diverged():
+                    raise RuntimeError("a token taken from the exported ids diverged")  # cannot happen
+            rng = sess.range_errors()
+            if rng:
+                from ..codec.errors import ArithmeticRangeError
+
+                raise ArithmeticRangeError(f"streams {rng[:8]}: a logits row the {mode} coder cannot code")
+            for b in range(B):
+                if active[b]:
+                    pos[b] += 1
+            nxt = [pos[b] < len(lists[b]) for b in range(B)]
+            if not any(nxt):
+                break
+            logits = self._lm_step(torch.tensor(feed, device=self.device, dtype=torch.long), nxt)
+        return sess.bits(), lists
+
     def reveal_spans(self, id_lists: Sequence[Sequence[int]], *, context: Optional[Sequence[int]] = None,
                      contexts: Optional[Sequence[Sequence[int]]] = None,
                      quality: Optional[Mapping[str, object]] = None,
@@ -1143,5 +1354,49 @@ def repair_or_restore(enc, inp: List[int], i: int, ranked_ids: Sequence[int], *,
         return int(ranked_ids[0])
 
 
+def huffman_repair(enc, inp: List[int], i: int, ranked_ids: Sequence[int]):
+    """``decode_huffman``'s BPE repair (code_base/huffman_baseline.py:108-149) over the K ranked leaders.  Line by
+    line it is the arithmetic decoder's (:func:`bpe_repair`): the 128 -> 198 case (:113), the ``<=`` prefix test
+    (:119), the longer-token merge with its deletion loop (:129-146), and rank 0 for an unrepairable token (:149)
+    while the LM is still fed the received one.  Returns ``(token to decode, repaired?)``."""
+    return bpe_repair(enc, inp, i, ranked_ids)
+
+
+def bins_repair(enc, inp: List[int], i: int, bin_tokens: Sequence[int]):
+    """``decode_block``'s BPE repair (code_base/block_baseline.py:140-181), restated line for line over
+    ``bin_tokens`` (every bin's token in bin order, the kernel's export).  It differs from the Huffman one: the
+    prefix test is strict (``<``, :154), there is no 128 -> 198 case, and the bits decoded are those of the loop
+    variable ``bin_num`` -- so an unrepairable token decodes as the LAST bin (:142,183) with ``inp`` untouched.
+    Edits ``inp`` in place as the reference does; returns ``(bin to decode, repaired?)``."""
+    true_token_text = enc.decode([inp[i]])
+    bin_num = 0
+    for bin_num, cand in enumerate(bin_tokens):
+        cand = int(cand)
+        prop_token_text = enc.decode([cand])
+        if len(prop_token_text) < len(true_token_text) and \
+                prop_token_text == true_token_text[:len(prop_token_text)]:
+            suffix = true_token_text[len(prop_token_text):]
+            suffix_tokens = enc.encode(suffix)
+            inp[i] = cand
+            inp[i + 1:i + 1] = suffix_tokens
+            return bin_num, True
+        elif len(prop_token_text) > len(true_token_text) and \
+                true_token_text == prop_token_text[:len(true_token_text)]:
+            whole_text = true_token_text
+            num_extra = 1
+            while len(whole_text) < len(prop_token_text):
+                whole_text += enc.decode([inp[i + num_extra]])
+                num_extra += 1
+            if prop_token_text == whole_text[:len(prop_token_text)]:
+                inp[i] = cand
+                for j in range(1, num_extra):
+                    del inp[i + j]
+                if len(whole_text) > len(prop_token_text):
+                    suffix = whole_text[len(prop_token_text):]
+                    inp[i + 1:i + 1] = enc.encode(suffix)
+                return bin_num, True
+    return bin_num, False
+
+
 __all__ = ["HipArithmeticLM", "ByteTokenizer", "coder_params_from_quality", "bpe_repair", "repair_or_restore",
-           "stop_candidates"]
+           "stop_candidates", "huffman_repair", "bins_repair"]

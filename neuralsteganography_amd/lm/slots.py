@@ -1639,3 +1639,84 @@ class SlotRevealer:
         ctx_host[slots] = tl
         len_host[slots] = nl
         return back
+
+
+class BaselineSlotEncoder(SlotEncoder):
+    """:class:`SlotEncoder` over a fixed-block baseline coder (``coder.BaselineEncodeSession``: the Huffman coder of
+    ``code_base/huffman_baseline.py`` or the bins coder of ``code_base/block_baseline.py``).  The loop -- admission,
+    one context per message, shared context pages and prefixes, the pipelined check, graph capture, eviction,
+    compaction -- is the parent's.  The step depends on nothing but the stream's own logits and payload, so a message
+    gives the tokens, bits and statistics of its one-message call in any slot, and an evicted message gives them
+    again."""
+
+    def __init__(self, provider, ctx, bit_lists, context, *, mode: str, block_size: int, slots: int, finish: bool,
+                 stats: bool, use_graph: bool, check_every: int = 16, compact: bool = True, contexts=None,
+                 share: bool = True, share_prefixes: bool = True, stall_steps: int = 4096):
+        max_bits = max(len(b) for b in bit_lists)
+        # a baseline stream consumes at least one bit per token; only a finish_sent tail can run on
+        super().__init__(provider, ctx, bit_lists, context, slots=slots, finish=finish, stop_text=None, stats=stats,
+                         check_every=check_every, stall_steps=stall_steps, hard_cap=max_bits + stall_steps + 64,
+                         use_graph=use_graph, compact=compact, contexts=contexts, share=share, qualities=None,
+                         share_prefixes=share_prefixes)
+        self.mode, self.block_size = mode, int(block_size)
+
+    def _session(self, S: int, budget: int, stride: int):
+        from ..coder import BaselineEncodeSession
+
+        return BaselineEncodeSession(self.ctx, self.bits[:S], mode=self.mode, block_size=self.block_size,
+                                     max_tokens=budget, stats=self.stats, payload_stride=stride)
+
+    def _range_error(self, msgs) -> str:
+        return f"messages {msgs}: a logits row the {self.mode} coder cannot code (NaN, inf or a bin without a token)"
+
+    def _key_extra(self, sess) -> tuple:
+        return _layout_key(sess.nbits, sess.out_token, sess.spec.table)
+
+
+class BaselineSlotDecoder(SlotSampler):
+    """:class:`SlotSampler`'s loop over a baseline decoder (``coder.BaselineDecodeStreamsSession``): a message's end is
+    known on the host from its token count, every slot reads the token at its own index from its device token row
+    (no host read in the loop), and every message has its own context.  ``run()`` returns each message's decoded
+    bits; a token outside the code raises :class:`DecodeDivergenceError` (the repairing decode is
+    ``HipArithmeticLM.decode_baseline_repair``)."""
+
+    def __init__(self, provider, ctx, token_lists, contexts, *, mode: str, block_size: int, slots: int,
+                 use_graph: bool, check_every: int = 16, compact: bool = True, share: bool = True,
+                 share_prefixes: bool = True):
+        n = len(token_lists)
+        super().__init__(provider, ctx, contexts, [len(t) for t in token_lists], None, [0] * n, [0] * n, slots=slots,
+                         use_graph=use_graph, stats=False, check_every=check_every, compact=compact, share=share,
+                         share_prefixes=share_prefixes)
+        self.lists = token_lists
+        self.mode, self.block_size = mode, int(block_size)
+
+    def _session(self, S: int, budget: int, Lmax: int):
+        from ..coder import BaselineDecodeStreamsSession
+
+        return BaselineDecodeStreamsSession(self.ctx, S, max_tokens=Lmax, mode=self.mode, block_size=self.block_size,
+                                            rank_export=False)
+
+    def _harvest(self, sess, fin, nl, ev, side, msgs):
+        from ..codec.errors import ArithmeticRangeError, DecodeDivergenceError
+        from ..coder import _bit_rows_to_lists
+
+        if ev is not None:
+            st, ob = _rows_after(ev, side, sess.state, fin), _rows_after(ev, side, sess.out_bits, fin)
+            f = _state_fields(st)
+            got, flags = _bit_rows_to_lists(ob, f["bit_pos"]), f["flags"]
+        else:
+            got, _, flags, _ = sess.harvest(fin)
+        bad = msgs[(flags & _lib.NS_ST_ERR_RANGE) != 0]
+        if bad.size:
+            raise ArithmeticRangeError(f"messages {bad.tolist()[:8]}: a logits row the {self.mode} coder cannot code")
+        bad = msgs[(flags & _lib.NS_ST_ERR_DIVERGE) != 0]
+        if bad.size:
+            raise DecodeDivergenceError(f"messages {bad.tolist()[:8]}: received token outside the {self.mode} code")
+        return got, None
+
+    def _key(self, sess) -> tuple:
+        return _layout_key(sess.state, sess.tokmat, sess.nlen, sess.out_bits, sess.counts, sess.out_token,
+                           sess.spec.table)
+
+    def _load(self, sess, slots, msgs, nl) -> None:
+        sess.load_slots(slots, [self.lists[m] for m in msgs])
